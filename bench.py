@@ -9,8 +9,13 @@ Each rank (one per GPU) verifies its own independent shard -- no
 collective on the data path ("scaling": "weak"); the only collective is
 the MAX over ranks of the timed interval.
 
-Printed (rank 0, one JSON line): value = all ranks' signatures / max
-rank time; roofline of the dominant kernel (fd_dsmh_kernel, the half-size walk: VALU integer,
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the
+K steps and prints the headline: value = all ranks' signatures / max rank
+time, ms_per_step, and the result codes checked against the generator's.
+`--dump-outputs DIR` writes the last timed step's result codes there, and
+the codes the same call gives for a seeded batch with invalid signatures.
+Everything else is behind `--full`, which prints the same headline plus:
+roofline of the dominant kernel (fd_dsmh_kernel, the half-size walk: VALU integer,
 priced in v_mad_u64_u32 multiply-accumulates against this device's own
 measured v_mad_u64_u32 peak); cpu_baseline = the reference's AVX-512
 fd_ed25519_verify (oracle/_ref, compiled from the reference sources) on
@@ -899,11 +904,14 @@ def compact_record(full: dict, detail_path: str | None) -> dict:
     rf = full.get("roofline") or {}
     cpu = full.get("cpu_baseline")
     rec = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-                                "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in full}
+                                "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "full") if k in full}
     cfg = full.get("config") or {}
     rec["config"] = {k: cfg[k] for k in ("workload", "txns_per_gpu", "sigs_per_gpu", "signed_msg_bytes", "parallelism",
                                          "semantics", "contexts_per_gpu") if k in cfg}
     rec["results_ok"] = full.get("results_ok")
+    if full.get("full") is False:        # a plain run (no --full): the headline is the whole record
+        rec["full"], rec["detail"] = False, detail_path
+        return rec
     rec["kernel_ms"] = {k: _r(v) for k, v in (full.get("kernel_ms") or {}).items()}
     rec["roofline"] = {
         "bound": rf.get("bound"), "kernel": rf.get("kernel"), "unit": rf.get("unit"),
@@ -1037,6 +1045,25 @@ def emit_record(full: dict, detail_path: str | None) -> str:
     return line
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files of a run together stay within this
+
+
+def dump_outputs(out_dir: str, rank: int, world: int, arrays: dict) -> list[str]:
+    """--dump-outputs: each array the timed path returned, as float32, in out_dir/<name>.npy (ranks above 0:
+    <name>_rank<r>.npy).  An array over this rank's share of DUMP_MAX_BYTES is cut to a fixed sample: the
+    elements at sorted indices drawn once from a seeded generator, the same in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(world, 1) // max(len(arrays), 1) // 4       # float32 elements per array
+    paths = []
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > budget:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, budget, replace=False))]
+        paths.append(os.path.join(out_dir, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"))
+        np.save(paths[-1], a.astype(np.float32))
+    return paths
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -1144,8 +1171,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--plan-cores", type=int, default=0,
                     help="(planning) host cores to budget the configs[4] stream children against instead of this "
                          "job's usable cores (e.g. --gpus 8 --dry-run --plan-cores 16)")
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps of the headline")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also every side measurement: the per-kernel roofline pass, the CPU "
+                         "baseline, the two-context steps, BASELINE configs[0,2,3], batch latency, the host-staged "
+                         "batch and the configs[4] stream legs, with the full record in --detail-out.  Without it the "
+                         "run sets up, warms up, times the steps and prints the headline line (no detail file)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned to DIR/<name>.npy (float32): "
+                         "txn_codes, one result code per transaction of the batch (all valid: zeros), and "
+                         "txn_codes_mixed, the same call's codes for a seeded batch of the same shape with 10 %% invalid "
+                         "signatures, run once after the timed steps (rank r > 0: <name>_rank<r>)")
     ap.add_argument("--txns", type=int, default=1 << 20, help="txns per GPU per step (BASELINE configs[1]: 1M)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--pipe", type=int, default=1,
@@ -1430,7 +1467,7 @@ def main():
 
     # --stream-first: the configs[4] legs before this process touches the GPU (its HIP context, queues and
     # torch's allocations then do not exist yet while the tile processes run)
-    stream = stream_section() if args.stream_frags != 0 and args.stream_first else None
+    stream = stream_section() if args.full and args.stream_frags != 0 and args.stream_first else None
     torch.cuda.set_device(dev)
 
     n = args.txns
@@ -1466,6 +1503,56 @@ def main():
     torch.cuda.synchronize()
     dt = shard.timed_steps(step, args.steps, 0, torch.cuda.synchronize, barrier)
     ok = all(bool(np.array_equal(o.cpu().numpy(), expect)) for _, _, o in pipe)
+    if args.dump_outputs:
+        # what the last timed step handed back: the batch's txn codes (the call asks for no per-signature codes).
+        # The timed batch is all valid, so those are all FD_ED25519_SUCCESS (0) and would not tell a working
+        # build from one whose kernels write nothing: the same call on the same context and stream, once more and
+        # untimed, over a batch of the same shape with 10 % seeded invalid signatures (BASELINE configs[2]'s
+        # recipe) gives codes that do
+        mp, md, m_expect, mn = synth.make_batch(n, synth.LARGE_NOOP, 1, 0.1, seed=shard.shard_seed(4321, rank),
+                                                threads=gen_threads)
+        mp_d, md_d = torch.from_numpy(mp).cuda(), torch.from_numpy(md.view(np.uint8)).cuda()
+        mo_d = torch.empty(n, dtype=torch.int8, device="cuda")
+        eng.verify_txns_device(mp_d.data_ptr(), md_d.data_ptr(), n, mn, mo_d.data_ptr(), None, st)
+        torch.cuda.synchronize()
+        mixed = mo_d.cpu().numpy()
+        ok = ok and bool(np.array_equal(mixed, m_expect))
+        dump_outputs(args.dump_outputs, rank, world, {"txn_codes": pipe[(step_i[0] - 1) % len(pipe)][2].cpu().numpy(),
+                                                      "txn_codes_mixed": mixed})
+        del mp_d, md_d, mo_d
+
+    def headline(dt_max, all_ok):
+        return {
+            "metric": "ed25519 verified sigs/sec at 1/8 MI355X vs host AVX-512; p99 batch latency",
+            "value": shard.aggregate_rate(world, nsig, args.steps, dt_max),
+            "unit": "sigs/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt_max * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32",
+            "data": "synthetic (fd_benchg large_noop layout, seeded ed25519 keys/signatures)",
+            "config": {"workload": "BASELINE configs[1]: 1M single-sig 1232-byte synthetic Solana txns, all valid",
+                       "txns_per_gpu": n, "sigs_per_gpu": nsig, "signed_msg_bytes": 1167,
+                       "parallelism": f"independent per-GPU shards x{world}", "semantics": "avx512",
+                       "contexts_per_gpu": args.pipe},
+            "results_ok": all_ok,
+            "full": bool(args.full),
+        }
+
+    if not args.full:
+        # a plain run ends here: the headline line alone (codes checked against the generator's, as above)
+        for e, _, _ in pipe:
+            e.close()
+        dt_max, all_ok = shard.reduce_max_min(dd, dt, ok, "cpu")
+        if rank == 0:
+            print(emit_record(headline(dt_max, all_ok), None), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # the roofline pass: a few more steps of the same batch with per-kernel HIP events on the launch stream
     # (the headline steps above run without event records between their kernels)
@@ -1678,25 +1765,8 @@ def main():
             cpu, impl, kind = cpu_baseline(payload, desc, nsig, threads=cores)
             cpu["cores_source"] = dict(core_src, used=cores)
             cpu["sweep_configs0"] = cpu_sweep_configs0(impl, kind, cores, gen_threads)
-        value = shard.aggregate_rate(world, nsig, args.steps, dt_max)
         rec = {
-            "metric": "ed25519 verified sigs/sec at 1/8 MI355X vs host AVX-512; p99 batch latency",
-            "value": value,
-            "unit": "sigs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt_max * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic (fd_benchg large_noop layout, seeded ed25519 keys/signatures)",
-            "config": {"workload": "BASELINE configs[1]: 1M single-sig 1232-byte synthetic Solana txns, all valid",
-                       "txns_per_gpu": n, "sigs_per_gpu": nsig, "signed_msg_bytes": 1167,
-                       "parallelism": f"independent per-GPU shards x{world}", "semantics": "avx512",
-                       "contexts_per_gpu": args.pipe},
-            "results_ok": all_ok,
+            **headline(dt_max, all_ok),
             "kernel_ms": {"prep": ms_prep, "dsm": ms_dsm, "reduce": ms_red, "decode": ms_dec, "hash": ms_hash,
                           "source": f"roofline pass: {ROOF_STEPS} more steps of the same batch, HIP events"},
             "roofline": {"bound": "valu", "achieved": achieved / 1e9, "peak": peak / 1e9, "unit": "GMAC/s",

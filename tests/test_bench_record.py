@@ -353,3 +353,79 @@ def test_served_max_leg_cfg():
     assert c["nctx"] == args.stream_ctx * args.stream_tiles     # the contexts of the one-process max leg's tiles
     args.stream_svc_max = 0
     assert "max" not in bench.stream_legs(args)
+
+
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """A run without --full prints the headline keys only (no roofline, CPU baseline or stream summaries) and
+    writes no detail file; the same record marked full keeps every summary."""
+    full = canned_full(n_gpus=1)
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                  "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "results_ok")}
+    rec = json.loads(bench.emit_record(dict(plain, full=False), None))
+    assert set(rec) == set(plain) | {"full", "detail"} and rec["full"] is False and rec["detail"] is None
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert rec[k] == full[k], k
+    rec = json.loads(bench.emit_record(dict(full, full=True), None))
+    assert rec["full"] is True and rec["roofline"]["frac"] and rec["stream"]["knee"] == 7.5e6
+
+
+def test_full_and_dump_outputs_options():
+    args = bench.parse_args([])
+    assert args.full is False and args.dump_outputs is None
+    args = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_dump_outputs_float32_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files named after the arrays (other ranks' with their rank), whole where they
+    fit; a larger array is cut to the same seeded sample in every run, within the 64 MB bound."""
+    import numpy as np
+    codes = (np.arange(1000) % 7 - 3).astype(np.int8)
+    (p,) = bench.dump_outputs(str(tmp_path / "a"), 0, 1, {"txn_codes": codes})
+    assert p == str(tmp_path / "a" / "txn_codes.npy")
+    a = np.load(p)
+    assert a.dtype == np.float32 and np.array_equal(a, codes.astype(np.float32))
+    (p1,) = bench.dump_outputs(str(tmp_path / "a"), 1, 2, {"txn_codes": codes})
+    assert os.path.basename(p1) == "txn_codes_rank1.npy"
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)                 # (the same cut at a size that is quick to write)
+    big = (np.arange((bench.DUMP_MAX_BYTES // 4) + 5) % 251).astype(np.uint8)
+    (q1,) = bench.dump_outputs(str(tmp_path / "b"), 0, 1, {"x": big})
+    (q2,) = bench.dump_outputs(str(tmp_path / "c"), 0, 1, {"x": big})
+    b1, b2 = np.load(q1), np.load(q2)
+    assert b1.dtype == np.float32 and b1.nbytes <= bench.DUMP_MAX_BYTES and b1.size == bench.DUMP_MAX_BYTES // 4
+    assert np.array_equal(b1, b2)
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    """One plain bench.py run on the GPU (a small batch, from an empty working directory), shared by the cases of
+    the test below: the process runs the product's defaults whatever engine path the case names."""
+    cwd = tmp_path_factory.mktemp("plain")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--txns", "2048", "--dump-outputs", "dump"],
+                       capture_output=True, text=True, timeout=120, cwd=str(cwd))
+    return r, cwd
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_codes(plain_run):
+    """bench.py without --full on the GPU: the headline line alone, no detail file, and --dump-outputs holding the
+    last step's txn codes (all valid: zeros) and the mixed batch's codes."""
+    import numpy as np
+    r, cwd = plain_run
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["full"] is False and rec["steps"] == 3 and rec["warmup"] == 1 and rec["results_ok"] is True
+    assert rec["unit"] == "sigs/s" and rec["higher_is_better"] is True and rec["dtype"] == "u32"
+    assert rec["ms_per_step"] > 0 and rec["value"] == pytest.approx(2048 * 1e3 / rec["ms_per_step"], rel=1e-6)
+    assert "roofline" not in rec and "stream" not in rec and "cpu_baseline" not in rec
+    assert os.listdir(cwd) == ["dump"] and sorted(os.listdir(cwd / "dump")) == ["txn_codes.npy", "txn_codes_mixed.npy"]
+    a = np.load(cwd / "dump" / "txn_codes.npy")
+    assert a.dtype == np.float32 and a.shape == (2048,) and not a.any()
+    # the same call over the seeded batch with invalid signatures: the generator's intended codes, not all zero
+    from firedancer_amd import shard, synth
+    _, _, expect, _ = synth.make_batch(2048, synth.LARGE_NOOP, 1, 0.1, seed=shard.shard_seed(4321, 0))
+    m = np.load(cwd / "dump" / "txn_codes_mixed.npy")
+    assert m.dtype == np.float32 and np.array_equal(m, expect.astype(np.float32))
+    assert 100 < np.count_nonzero(m) < 400 and len(np.unique(m)) > 2

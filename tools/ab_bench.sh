@@ -4,7 +4,7 @@
 # Each run prints one line: name value dsm prep.  Reps alternate the order (ABBA).
 reps="$1"; shift
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-B="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
+B="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
 for r in $(seq "$reps"); do
   # odd reps run the list forward, even reps backward (ABBA): an order effect cancels over pairs
   if (( r % 2 )); then order=("$@"); else order=(); for (( i=$#; i>=1; i-- )); do order+=("${!i}"); done; fi

@@ -5,7 +5,7 @@
 # usage (GPU box): bash tools/dsm_ab.sh <variant> ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/dsm_ab
-B="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
+B="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
 specs=()
 for rep in 1 2; do
   for v in "$@"; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # headline A/B: consecutive 1M-signature steps on one context vs alternating over two (--pipe 2)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-B="python3 bench.py --steps 20 --warmup 4 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
+B="python3 bench.py --full --steps 20 --warmup 4 --no-cpu-baseline --latency-batch 0 --stream-frags 0 --no-extra-configs"
 mkdir -p gpurun_out
 for r in 1 2 3; do
   for p in 1 2 3; do
