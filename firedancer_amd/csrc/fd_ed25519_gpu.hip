@@ -16,6 +16,12 @@
                        FD_ED25519_SUCCESS / ERR_MSG
      fd_reduce_kernel  per transaction: fd_ed25519_verify_batch_single_msg
                        code from its signatures' codes
+     large batches (the half-size throughput path) split
+     the prep: fd_keydedup_kernel (a representative signature per distinct
+     public key of the batch), fd_decode_kernel (roles by block: A and its
+     table for the representatives, R and its table for every signature),
+     fd_hashh_kernel (codes, SHA-512, the half-size scalars), then the walk
+     fd_dsmh_kernel (-A entries gathered at the representative's index)
      fd_parse_kernel   (raw-payload batches) per transaction: fd_txn_parse,
                        fd_txn_t image, and the descriptor the kernels
                        above consume
@@ -125,6 +131,9 @@
 #define FD_HALF_FUSED_TABLE 1      /* half-size throughput path: tables built by the decode lanes (0: fd_tableh_kernel) */
 #endif
 #define FD_PSTAT_SLOW 0x80u        /* A-status bit: the signature is on the half-size path's slow list */
+/* fd_keydedup_kernel: workgroups (of sg) whose lanes still look their keys up when the batch before had
+   mostly distinct keys -- the sample that decides for the batch after */
+#define FD_KD_SBLK( sg ) ( (sg) >> 4 ? (sg) >> 4 : 1u )
 
 typedef signed char i8;
 
@@ -203,7 +212,8 @@ __global__ void __launch_bounds__( FD_WG )
 fd_expand_kernel( fdgpu_txn_desc_t const * __restrict__ desc, u32 txn_cnt, u32 * __restrict__ map, u32 nsig,
                   u32 * __restrict__ zero_word ) {
   u32 t = blockIdx.x * FD_WG + threadIdx.x;
-  if( zero_word && t == 0u ) *zero_word = 0u;        /* the batch's slow-list count (half-size path) */
+  if( zero_word && t == 0u ) { zero_word[0] = 0u; zero_word[1] = 0u; }   /* the batch's slow-list count and its count
+                                                                            of distinct keys (half-size path) */
   if( t >= txn_cnt ) return;
   fdgpu_txn_desc_t d = desc[t];
   for( u32 j=0; j<d.sig_cnt; j++ ) {
@@ -261,22 +271,22 @@ FD_DEV int txn_desc_ok( fdgpu_txn_desc_t const & d ) {
 /* Stage 1 -- point decompression of signature s's public key A (is_r 0)
    or its R (is_r 1).  Status byte rc | small_order<<2 (rc: 0 ok, 1 not
    a square, 2 x==0 with sign set), 0xff if the transaction is
-   malformed; the canonical affine point goes to Axy / Rxy. */
+   malformed, stored at *stat; the canonical affine point goes to Axy / Rxy. */
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void decode_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
-                        u32 const * __restrict__ map, u32 s, u32 is_r, unsigned char * __restrict__ pstat,
+                        u32 const * __restrict__ map, u32 s, u32 is_r, unsigned char * __restrict__ stat,
                         uint4 * __restrict__ Rxy, uint4 * __restrict__ Axy ) {
   u32 m = map[s];
   u32 t = m & 0xffffffu, j = m >> 24;
   fdgpu_txn_desc_t d = desc[t];
-  if( !txn_desc_ok( d ) ) { pstat[2u*s + is_r] = 0xffu; return; }
+  if( !txn_desc_ok( d ) ) { *stat = 0xffu; return; }
   unsigned char const * base = payload + d.payload_off;
   u32 w[8];
   fd_load_words<8>( w, base + ( is_r ? (u32)d.signature_off + 64u*j : (u32)d.acct_addr_off + 32u*j ) );
   ge_p3 P; int rc;
   ge_decode1<FM>( P, rc, w );
   int so = ge_affine_is_small_order( P );
-  pstat[2u*s + is_r] = (unsigned char)( rc | (so << 2) );
+  *stat = (unsigned char)( rc | (so << 2) );
   u32 x[8], y[8];
   fe_pack( x, P.X ); fe_pack( y, P.Y );
   uint4 * o = ( is_r ? Rxy : Axy ) + (size_t)s*4;
@@ -304,15 +314,46 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
                   uint4 *                  __restrict__ Rxy,
                   uint4 *                  __restrict__ Axy,
                   uint4 *                  __restrict__ tabA,
-                  uint4 *                  __restrict__ tabR ) {
-  u32 p = blockIdx.x * FD_WG + threadIdx.x;
-  if( p >= ( both ? 2u*nsig : nsig ) ) return;
-  u32 s = both ? p >> 1 : p, is_r = both ? p & 1u : 0u;
-  decode_one<FD_DECODE_FM>( payload, desc, map, s, is_r, pstat, Rxy, Axy );
+                  uint4 *                  __restrict__ tabR,
+                  u32 const *              __restrict__ ulist,
+                  u32 *                    __restrict__ ucnt,
+                  unsigned char *          __restrict__ astat,
+                  u32                                   ublk ) {
+  u32 s, is_r;
+  unsigned char * st;
+  if( ulist ) {
+    /* keys de-duplicated (fd_keydedup_kernel): roles by block.  Blocks [0,ublk) decode A for the batch's
+       representatives only -- the grid holds the worst case, blocks beyond the count on the device return at
+       once -- and write A's point, status (astat, read-only from here on) and table at the representative's
+       index; blocks [ublk,..) decode R for every signature */
+    if( blockIdx.x < ublk ) {
+      u32 i = blockIdx.x * FD_WG + threadIdx.x;
+      u32 cnt = ucnt[0];
+      /* for the next batch's fd_keydedup_kernel: were more than 7/8 of this one's signatures representatives?  (Of
+         its sample, when this batch was not de-duplicated in full.) */
+      if( !i ) {
+        u32 samp = FD_KD_SBLK( ublk ) * FD_WG; samp = samp < nsig ? samp : nsig;
+        ucnt[1] = ucnt[1] ? ucnt[2] > samp - ( samp >> 3 ) : cnt > nsig - ( nsig >> 3 );
+        ucnt[2] = 0u;
+      }
+      if( i >= cnt ) return;
+      s = ulist[i]; is_r = 0u; st = astat + s;
+    } else {
+      s = ( blockIdx.x - ublk ) * FD_WG + threadIdx.x; is_r = 1u;
+      if( s >= nsig ) return;
+      st = pstat + 2u*s + 1u;
+    }
+  } else {
+    u32 p = blockIdx.x * FD_WG + threadIdx.x;
+    if( p >= ( both ? 2u*nsig : nsig ) ) return;
+    s = both ? p >> 1 : p; is_r = both ? p & 1u : 0u;
+    st = pstat + 2u*s + is_r;
+  }
+  decode_one<FD_DECODE_FM>( payload, desc, map, s, is_r, st, Rxy, Axy );
   /* tabA != NULL (half-size path): each lane goes on to its point's table
      when the point decoded, its table writes overlapping the other waves'
      decodes (a separate table kernel is write-heavy: 2.3 KB per signature) */
-  if( tabA && ( pstat[2u*s + is_r] & 3u )==0u ) atab_build<FD_TABLE_FM>( is_r ? tabR : tabA, s, is_r ? Rxy : Axy );
+  if( tabA && ( *st & 3u )==0u ) atab_build<FD_TABLE_FM>( is_r ? tabR : tabA, s, is_r ? Rxy : Axy );
 }
 
 /* Signed digits of k (radix 16, digA[64][n]) and S (radix 2^FD_BWIN,
@@ -555,7 +596,8 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
                        unsigned char * __restrict__ pstat, i8 * __restrict__ code_out, i8 * __restrict__ digA,
                        i8 * __restrict__ digR, short * __restrict__ digB, u32 * __restrict__ slow,
                        u32 * __restrict__ slow_cnt, uint4 const * __restrict__ khash, u32 force_slow,
-                       unsigned char * __restrict__ htop ) {
+                       unsigned char * __restrict__ htop, u32 const * __restrict__ arep = (u32 const *)0,
+                       unsigned char const * __restrict__ astat = (unsigned char const *)0 ) {
   u32 m = map[s];
   u32 t = m & 0xffffffu, j = m >> 24;
   fdgpu_txn_desc_t d = desc[t];
@@ -564,7 +606,10 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
   u32 Sw[8];
   fd_load_words<8>( Sw, base + d.signature_off + 64u*j + 32u );
   int code = sc_is_canonical( Sw ) ? FD_ED25519_SUCCESS : FD_ED25519_ERR_SIG;
-  if( rc ) code = result_code( code, pstat[2*s], pstat[2*s+1], semantics, 0 );
+  /* arep (keys de-duplicated): A's status is the representative's, in an array nothing writes after the
+     decode -- pstat[2s] then holds only this signature's own FD_PSTAT_SLOW flag, which a representative's
+     lane may set while another signature of its key reads A's status */
+  if( rc ) code = result_code( code, arep ? astat[ arep[s] ] : pstat[2*s], pstat[2*s+1], semantics, 0 );
   if( code != FD_ED25519_SUCCESS ) { code_out[s] = (i8)code; return; }
   u32 Rw[8], Aw[8];
   fd_load_words<8>( Rw, base + d.signature_off + 64u*j );
@@ -662,11 +707,13 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  u32 *                    __restrict__ slow_cnt,
                  uint4 const *            __restrict__ khash,
                  u32                                   force_slow,
-                 unsigned char *          __restrict__ htop ) {
+                 unsigned char *          __restrict__ htop,
+                 u32 const *              __restrict__ arep,
+                 unsigned char const *    __restrict__ astat ) {
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
   hashh_one( payload, desc, map, s, nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt, khash,
-             force_slow, htop );
+             force_slow, htop, arep, astat );
 }
 
 /* FD_SHA_SPLIT (A/B): the half-size throughput path hashes in a kernel of its own, at the occupancy the
@@ -714,7 +761,7 @@ FD_DEV void prep_role( unsigned char const * __restrict__ payload, fdgpu_txn_des
                        i8 * __restrict__ digR, u32 * __restrict__ slow, u32 * __restrict__ slow_cnt, u32 force_slow,
                        unsigned char * __restrict__ htop ) {
   if( role < 2u ) {
-    decode_one<FM>( payload, desc, map, s, role, pstat, Rxy, Axy );
+    decode_one<FM>( payload, desc, map, s, role, pstat + 2u*s + role, Rxy, Axy );
     /* tab != NULL: the A lane goes on to the -A table (for every A that
        decoded; fd_dsm2_kernel applies the result-code procedure); HS: the R
        lane to the -R table */
@@ -860,7 +907,7 @@ __device__ unsigned long long fd_clk_buf[ FD_CLK_BLOCKS ][ 4 ];
 template<int FM>
 FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 const * __restrict__ Rxy,
                      i8 const * __restrict__ digA, short const * __restrict__ digB, uint4 const * btab,
-                     i8 * __restrict__ code, u32 * __restrict__ Pbuf, int defer ) {
+                     i8 * __restrict__ code, u32 * __restrict__ Pbuf, int defer, u32 sa ) {   /* sa: whose -A table */
   ge_p3 P; ge_p3_identity( P );
   ge_p2 P2;
   atab_raw raw;
@@ -872,7 +919,7 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
 #pragma unroll 1
   for( int w=63; w>=0; w-- ) {
 #if FD_DSM_PREFETCH
-    atab_fetch( raw, tab, s, da < 0 ? -da : da );   /* in flight during the doublings */
+    atab_fetch( raw, tab, sa, da < 0 ? -da : da );   /* in flight during the doublings */
 #endif
 #if FD_BWIN==16
     if( !(w & 3) ) {                                 /* base-point entry, also in flight */
@@ -890,7 +937,7 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
     }
     {
 #if !FD_DSM_PREFETCH
-      atab_fetch( raw, tab, s, da < 0 ? -da : da );
+      atab_fetch( raw, tab, sa, da < 0 ? -da : da );
 #endif
       ge_cached q; atab_unpack( q, raw ); ge_cached_cneg( q, da < 0 );
       ge_add_cached<FM>( t, P, q );
@@ -967,7 +1014,7 @@ fd_dsm_kernel( u32                      nsig,
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
   if( code[s] != FD_ED25519_SUCCESS ) return;
-  dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, Pbuf, defer );
+  dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, Pbuf, defer, s );
   FD_CLK_END
 }
 
@@ -981,9 +1028,9 @@ __global__ void __launch_bounds__( FD_WG )
 fd_dsm_slow_kernel( u32 nsig, uint4 const * __restrict__ tab, uint4 const * __restrict__ Rxy,
                     i8 const * __restrict__ digA, short const * __restrict__ digB, uint4 const * __restrict__ btab,
                     i8 * __restrict__ code, u32 const * __restrict__ slow, u32 const * __restrict__ slow_cnt,
-                    u32 first ) {
+                    u32 first, u32 const * __restrict__ arep ) {
   u32 i = first + blockIdx.x * FD_WG + threadIdx.x;
-  if( i < *slow_cnt ) dsm_one<FM>( slow[i], nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0 );
+  if( i < *slow_cnt ) { u32 s = slow[i]; dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[s] : s ); }
 }
 
 /* Latency half-size path: the slow list after the walks, the result-code
@@ -1001,7 +1048,7 @@ FD_DEV void slowl_tail( u32 nsig, uint4 const * __restrict__ tab, uint4 const * 
     if( code[s] != FD_PEND_SLOW ) continue;
     int c = result_code( FD_ED25519_SUCCESS, pstat[2*s], pstat[2*s+1], semantics, 0 );
     if( c != FD_ED25519_SUCCESS ) { code[s] = (i8)c; continue; }
-    dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0 );
+    dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, s );
   }
 }
 
@@ -1063,14 +1110,15 @@ fd_dsmh_kernel( u32                      nsig,
                 unsigned char const * __restrict__ pstat,
                 unsigned char const * __restrict__ htop,
                 int                        rc,
-                int                        semantics ) {
+                int                        semantics,
+                u32 const *   __restrict__ arep ) {      /* keys de-duplicated: -A's table is at arep[s], else NULL */
   size_t n = nsig;
   if( blockIdx.x < nslowblk ) {
     /* the first blocks take the head of the slow list (full 253-bit walk,
        about twice a half-size walk): dispatched first, they run beside the
        half-size waves instead of after them; fd_dsm_slow_kernel takes the rest */
     u32 i = blockIdx.x * FD_WG + threadIdx.x;
-    if( i < *slow_cnt ) dsm_one<FM>( slow[i], n, tabA, Rxy, digA, digB, btab, code, (u32 *)0, 0 );
+    if( i < *slow_cnt ) { u32 ss = slow[i]; dsm_one<FM>( ss, n, tabA, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[ss] : ss ); }
     return;
   }
   u32 s = ( blockIdx.x - nslowblk ) * FD_WG + threadIdx.x;
@@ -1089,10 +1137,11 @@ fd_dsmh_kernel( u32                      nsig,
   ge_p3 P; ge_p3_identity( P );
   ge_p2 P2;
   atab_raw ra, rr;
+  u32 sa = arep ? arep[s] : s;
   int da = digA[ (size_t)wtop*n + s ], dr = digR[ (size_t)wtop*n + s ];
 #pragma unroll 1
   for( int w=wtop; w>=0; w-- ) {
-    atab_fetch( ra, tabA, s, da < 0 ? -da : da );    /* in flight during the doublings */
+    atab_fetch( ra, tabA, sa, da < 0 ? -da : da );    /* in flight during the doublings */
     ge_p1p1 t;
     if( w != wtop ) {
 #pragma unroll 1
@@ -2056,6 +2105,125 @@ FD_DEV u64 fd_xxh64_64( u64 seed, unsigned char const * p ) {
   return h;
 }
 
+/* Half-size throughput path: each distinct public key of a batch is decoded once.  A's point, status and
+   -A table depend on the 32 key bytes alone, and a batch holds far fewer keys than signatures (votes, a few
+   fee payers), so one lane per signature looks its key up in an open-addressed table in HBM (ktab, a power
+   of two of 32-bit slots, at least twice the batch's signatures) and the A lanes of fd_decode_kernel run
+   over the representatives only.
+     slot   0 = empty, else 1 + the signature that claimed it.  launch_batch clears the part of the table
+            the batch uses with a memset on the stream ahead of this kernel (8 MB for 1M signatures, a few
+            microseconds), so a claim is one blind compare-and-swap of 0 whose return value names the
+            claimant -- no tag to read first, nothing left over from the batch before;
+     probe  linear from the key's hash (XXH64's rounds over the four words, seeded per batch), at most
+            `probes` slots.  Normally a lane first reads the slot with an ordinary load, so the lanes of a key
+            already in the table (nearly all of them) do no atomic at all: a stale 0 only sends the lane
+            to the compare-and-swap, which answers with the truth.  A taken slot names a signature whose 32
+            key bytes are read back from the payload and compared -- a hash match alone never counts.  A
+            lane that runs out of probes is its own representative: decoded on its own, which is what every
+            lane did before, so no input makes this kernel spin or chain;
+     bypass when nearly every key of a batch is distinct nothing can be saved, and a million claims cost
+            0.11-0.13 ms of random accesses per 1M signatures (the key's line, the slot).  The count is known
+            only after this kernel, so the verdict comes from the context's previous batch (traffic does not
+            change its nature from batch to batch), through the word behind *ucnt, never through the host:
+            fd_decode_kernel sets it when more than 7/8 of the signatures were representatives (below that the
+            A decodes saved, 1.2 ms per 1M at none distinct, outweigh the claims).  While it
+            is set only the lanes of the first FD_KD_SBLK workgroups (1/16 of the batch) look their keys up
+            -- claiming blindly, without the read -- and every other lane is its own representative without
+            touching its key or the table; the sample's share of representatives (ucnt[2]) decides whether
+            the next batch is de-duplicated in full again.  Either way every arep[] names a lane that
+            decodes that very key, so the results are the same;
+     out    arep[s] = s's representative (s itself for a representative and for a malformed transaction,
+            which takes no part), ulist[] = the representatives, compacted with one atomic add per
+            workgroup (the waves' counts meet in LDS), *ucnt their number, and pstat[2s] = 0: with shared
+            keys that byte holds only the signature's own FD_PSTAT_SLOW flag, A's status lives at
+            astat[arep[s]].
+   Which of a key's signatures wins its slot differs from run to run; every one of them gives the same
+   point, status and table. */
+#define FD_KD_PROBES 16u
+__global__ void __launch_bounds__( FD_WG )
+fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
+                    fdgpu_txn_desc_t const * __restrict__ desc,
+                    u32 const *              __restrict__ map,
+                    u32                                   nsig,
+                    u32 *                    __restrict__ ktab,
+                    u32                                   kmask,
+                    u32                                   seed32,
+                    u32                                   probes,
+                    u32 *                    __restrict__ arep,
+                    u32 *                    __restrict__ ulist,
+                    u32 *                    __restrict__ ucnt,
+                    unsigned char *          __restrict__ pstat,
+                    u32                                   sblk ) {
+  __shared__ u32 wcnt[ FD_WG / 64 + 1 ];
+  u32 s = blockIdx.x * FD_WG + threadIdx.x;
+  int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
+  int peek = !bypass;
+  int own = s < nsig;
+  u32 rep = s;
+  if( s < nsig ) {
+    pstat[2u*s] = 0u;
+    u32 m = map[s];
+    fdgpu_txn_desc_t d = desc[m & 0xffffffu];
+    if( ( !bypass || blockIdx.x < sblk ) && txn_desc_ok( d ) ) {
+      u32 w[8];
+      fd_load_words<8>( w, payload + d.payload_off + (u32)d.acct_addr_off + 32u*( m >> 24 ) );
+      u64 seed = (u64)seed32 * FD_XXP3;
+      u64 v0 = fd_xxh_round( seed + FD_XXP1 + FD_XXP2, ((u64)w[1] << 32) | (u64)w[0] );
+      u64 v1 = fd_xxh_round( seed + FD_XXP2,           ((u64)w[3] << 32) | (u64)w[2] );
+      u64 v2 = fd_xxh_round( seed,                     ((u64)w[5] << 32) | (u64)w[4] );
+      u64 v3 = fd_xxh_round( seed - FD_XXP1,           ((u64)w[7] << 32) | (u64)w[6] );
+      u64 h = fd_rotl64( v0, 1 ) + fd_rotl64( v1, 7 ) + fd_rotl64( v2, 12 ) + fd_rotl64( v3, 18 );
+      h ^= h >> 33; h *= FD_XXP2; h ^= h >> 29; h *= FD_XXP3; h ^= h >> 32;
+      for( u32 i=0; i<probes; i++ ) {
+        u32 * slot = ktab + ( ( (u32)h + i ) & kmask );
+        u32 v = peek ? __hip_atomic_load( slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP ) : 0u;   /* an ordinary load */
+        if( !v ) {
+          v = atomicCAS( slot, 0u, s + 1u );
+          if( !v ) break;                            /* claimed */
+        }
+        u32 c = v - 1u;                              /* taken: the same key? */
+        if( c >= nsig ) continue;
+        u32 mc = map[c];
+        fdgpu_txn_desc_t dc = desc[mc & 0xffffffu];
+        u32 wc[8];
+        fd_load_words<8>( wc, payload + dc.payload_off + (u32)dc.acct_addr_off + 32u*( mc >> 24 ) );
+        u32 diff = 0u;
+#pragma unroll
+        for( int k=0; k<8; k++ ) diff |= w[k] ^ wc[k];
+        if( !diff ) { rep = c; own = 0; break; }
+      }
+    }
+    arep[s] = rep;
+  }
+  /* the workgroup's representatives, appended with one atomic add: each wave's count to LDS, thread 0
+     adds their sum, every lane takes its wave's base + its rank in the wave */
+  unsigned long long mk = __ballot( own );
+  u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  if( !lane ) wcnt[wv] = (u32)__popcll( mk );
+  __syncthreads();
+  /* bypass: the lanes behind the sample are all representatives and take the list's head in order, with
+     no atomic that anything waits for; the sample's follow, placed by the sample's own counter */
+  u32 nsamp = sblk * FD_WG < nsig ? sblk * FD_WG : nsig;
+  if( !threadIdx.x ) {
+    u32 tot = 0u;
+    for( u32 k=0; k<FD_WG/64; k++ ) { u32 c = wcnt[k]; wcnt[k] = tot; tot += c; }
+    u32 base = 0u;
+    if( !bypass ) {
+      if( tot ) base = atomicAdd( ucnt, tot );
+      if( tot && blockIdx.x < sblk ) atomicAdd( ucnt + 2, tot );     /* the sample's representatives */
+    } else if( blockIdx.x < sblk ) {
+      if( tot ) { base = ( nsig - nsamp ) + atomicAdd( ucnt + 2, tot ); atomicAdd( ucnt, tot ); }
+      if( !blockIdx.x && nsig > nsamp ) atomicAdd( ucnt, nsig - nsamp );
+    }
+    wcnt[ FD_WG/64 ] = base;
+  }
+  __syncthreads();
+  if( own ) {
+    if( bypass && blockIdx.x >= sblk ) ulist[ s - nsamp ] = s;
+    else ulist[ wcnt[ FD_WG/64 ] + wcnt[wv] + (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) ) ] = s;
+  }
+}
+
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
    (the verify service's batches hold several tiles' frags, each tile with its own secure seed,
    fd_verify_tile.c:166) */
@@ -2080,7 +2248,8 @@ fd_parse_kernel( unsigned char const *    __restrict__ payload,
   u32 t = blockIdx.x * FD_WG + threadIdx.x;
   if( t == 0u ) {
     if( stamp ) __hip_atomic_store( stamp, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-    if( zero_word ) *zero_word = 0u;                 /* the batch's slow-list count (half-size path) */
+    if( zero_word ) { zero_word[0] = 0u; zero_word[1] = 0u; }   /* the batch's slow-list count and its count of
+                                                                   distinct keys (half-size path) */
   }
   if( t >= txn_cnt ) return;
   fdgpu_txn_raw_t r = raw[t];
@@ -2382,6 +2551,15 @@ struct fdgpu_ed25519_ctx {
   uint4 * d_btab2;               /*                 [0..32768](2^120 B) */
   uint4 * d_khash;               /* NULL, or (drop-in, long messages) SHA-512(R||A||M) per signature, computed beforehand */
   uint4 * d_kdig;                /* FD_SHA_SPLIT: fd_sha_kernel's digests, [max_sig][4] */
+  int     key_dedup;             /* half-size throughput path: distinct keys decoded once.  The resolved choice, 1 = on,
+                                    0 = off -- not the value of fdgpu_debug_opts_t.key_dedup (0 on, 1 off, 2 tests) */
+  u32 *   d_ktab;                /*   fd_keydedup_kernel's table, kd_slots 32-bit slots (>= 2 max_sig: load <= 0.5) */
+  u32     kd_slots, kd_probes;   /*   slots allocated (a power of two); probes per lane */
+  int     kd_tiny;               /*   fdgpu_debug_opts_t.key_dedup = 2: every batch uses all (64) slots */
+  u32     kd_seed;               /*   batches launched: the hash seed (any value is right; it only varies the probes) */
+  u32 *   d_arep;                /*   [max_sig] each signature's representative */
+  u32 *   d_ulist;               /*   [max_sig] the representatives + their count */
+  unsigned char * d_astat;       /*   [max_sig] A's status, at the representative's index */
   hipEvent_t ev[5];
   enum { NRING = 64 };
   hipEvent_t ring[ NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
@@ -2623,11 +2801,27 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
       /* half-size scalars: decode A and R, result codes + hash + (c0, c1, s'), both tables */
       unsigned pg = (unsigned)( ( 2UL*sig_cnt + FD_WG - 1) / FD_WG );
 #if FD_HALF_FUSED_TABLE
+      if( ctx->key_dedup ) {
+        /* each distinct key decoded once: the table cleared for this batch -- the smallest power of two of
+           slots that is twice its signatures, so a small batch on a large context clears little -- then A
+           lanes over the representatives, R lanes over every signature */
+        u32 slots = 64u;
+        if( !ctx->kd_tiny ) while( slots < ctx->kd_slots && slots < 2u*nsig ) slots <<= 1;
+        HIPCHK( hipMemsetAsync( ctx->d_ktab, 0, (size_t)slots * sizeof(u32), st ), -3 );
+        hipLaunchKernelGGL( fd_keydedup_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
+                            ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep, ctx->d_ulist,
+                            ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ) );
+        hipLaunchKernelGGL( fd_decode_kernel, dim3(2*sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
+                            ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR, (u32 const *)ctx->d_ulist,
+                            ctx->d_slow + ctx->max_sig + 1, ctx->d_astat, (u32)sg );
+      } else
       hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR );
+                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR, (u32 const *)NULL,
+                          (u32 *)NULL, (unsigned char *)NULL, 0u );
 #else
       hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL );
+                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
+                          (u32 *)NULL, (unsigned char *)NULL, 0u );
 #endif
       if( ctx->timing ) hipEventRecord( ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
       uint4 const * kh = (uint4 const *)ctx->d_khash;
@@ -2637,7 +2831,9 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
       }
       hipLaunchKernelGGL( fd_hashh_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
                           ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_slow,
-                          ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop );
+                          ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop,
+                          (u32 const *)( ctx->key_dedup ? ctx->d_arep : NULL ),
+                          (unsigned char const *)( ctx->key_dedup ? ctx->d_astat : NULL ) );
 #if !FD_HALF_FUSED_TABLE
       hipLaunchKernelGGL( fd_tableh_kernel, dim3(2*sg), dim3(FD_WG), 0, st, nsig, (u32)sg, code, ctx->d_Axy, ctx->d_Rxy,
                           ctx->d_tab, ctx->d_tabR );
@@ -2646,7 +2842,8 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
       ctx->last_path = FDGPU_PATH_THROUGHPUT_FULL;
       unsigned pg = (unsigned)( ( (defer ? 1UL : 2UL)*sig_cnt + FD_WG - 1) / FD_WG );
       hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, !defer,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL );
+                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
+                          (u32 *)NULL, (unsigned char *)NULL, 0u );
       hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
                           ctx->semantics, defer, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
                           (uint4 const *)ctx->d_khash );
@@ -2671,26 +2868,27 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
     else if( hs )                              /* one lane: the half-size walk, result codes at its start */
       hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                           ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow,
-                          ctx->d_slow + ctx->max_sig, 0u, ctx->d_pstat, ctx->d_htop, 1, ctx->semantics );
+                          ctx->d_slow + ctx->max_sig, 0u, ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL );
     else if( half ) {
       /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the
          rest (if any) in fd_dsm_slow_kernel */
       unsigned nsb = ( sg + 63u ) / 64u;
       u32 * slow_cnt = ctx->d_slow + ctx->max_sig;
+      u32 const * arep = ctx->key_dedup ? ctx->d_arep : NULL;     /* -A's tables at the representatives */
       if( nsig <= ctx->nofold_max ) {
         hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(nsb + sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                             ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
-                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics );
+                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep );
         if( ctx->timing ) hipEventRecord( ev[2], st );
         hipLaunchKernelGGL( fd_dsm_slow_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
-                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG );
+                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG, arep );
       } else {
         hipLaunchKernelGGL( fd_dsmh_kernel<1>, dim3(nsb + sg), dim3(FD_WG), FD_DSMH_LDS, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                             ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
-                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics );
+                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep );
         if( ctx->timing ) hipEventRecord( ev[2], st );
         hipLaunchKernelGGL( fd_dsm_slow_kernel<1>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
-                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG );
+                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG, arep );
       }
     }
     else if( nsig <= ctx->nofold_max )         /* <= 2 waves per SIMD: latency-bound, independent column chains */
@@ -2727,14 +2925,14 @@ static void launcher_drain( fdgpu_launcher_t * L );
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
 fdgpu_debug_set_opts( fdgpu_debug_opts_t const * opts ) {
   std::lock_guard<std::mutex> lk( g_dbg_mu );
   if( opts ) g_dbg = *opts;
-  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0 };
+  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0 };
 }
 
 /* staging + device buffers of async slot i (once) */
@@ -2801,7 +2999,10 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   HIPCHK( hipMalloc( &ctx->d_P, ns * 30 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_O, ns * 10 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_blk, ( ( ns + FD_WG - 1 ) / FD_WG ) * 10 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + 1 ) * sizeof(u32) ), -1 );
+  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + 4 ) * sizeof(u32) ), -1 );   /* + the slow count, the distinct-key count, whether
+                                                                           most keys of the last batch were distinct, and the
+                                                                           sample's count (fd_keydedup_kernel) */
+  HIPCHK( hipMemsetAsync( ctx->d_slow + ns, 0, 4 * sizeof(u32), ctx->stream ), -1 );
   fdgpu_debug_opts_t dbg; debug_opts_get( &dbg );   /* test / A/B choices (fdgpu_debug_set_opts), never the environment */
   ctx->half = dbg.half >= 0 ? dbg.half : FD_HALF;
   ctx->half_force_slow = dbg.half_force_slow;
@@ -2811,6 +3012,18 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
     HIPCHK( hipMalloc( &ctx->d_htop, ns ), -1 );
     if( FD_SHA_SPLIT ) HIPCHK( hipMalloc( &ctx->d_kdig, ns * 4 * sizeof(uint4) ), -1 );
     HIPCHK( hipMalloc( &ctx->d_btab2, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+    /* distinct keys decoded once (needs the decode lanes to build the tables: FD_HALF_FUSED_TABLE) */
+    ctx->key_dedup = FD_HALF_FUSED_TABLE && dbg.key_dedup != 1;
+    if( ctx->key_dedup ) {
+      unsigned long slots = 64UL;                    /* fdgpu_debug_opts_t.key_dedup = 2 (tests): 64 slots, 2 probes */
+      if( dbg.key_dedup != 2 ) while( slots < 2UL*ns && slots < ( 1UL << 31 ) ) slots <<= 1;
+      ctx->kd_slots = (u32)slots; ctx->kd_tiny = dbg.key_dedup == 2; ctx->kd_probes = ctx->kd_tiny ? 2u : FD_KD_PROBES;
+      ctx->kd_seed = 0u;
+      HIPCHK( hipMalloc( &ctx->d_ktab, slots * sizeof(u32) ), -1 );           /* (cleared per batch, launch_batch) */
+      HIPCHK( hipMalloc( &ctx->d_arep, ns * sizeof(u32) ), -1 );
+      HIPCHK( hipMalloc( &ctx->d_ulist, ns * sizeof(u32) ), -1 );
+      HIPCHK( hipMalloc( &ctx->d_astat, ns ), -1 );
+    }
   }
   ctx->small_max  = dbg.small_batch_max >= 0 ? (unsigned long)dbg.small_batch_max : FD_SMALL_BATCH_MAX;
   ctx->dsm_lanes  = dbg.dsm_lanes;
@@ -2879,6 +3092,7 @@ fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx ) {
   (void)hipFree( ctx->d_btab ); (void)hipFree( ctx->d_rdesc ); (void)hipFree( ctx->d_pflag );
   (void)hipFree( ctx->d_tabR ); (void)hipFree( ctx->d_digR ); (void)hipFree( ctx->d_htop ); (void)hipFree( ctx->d_btab2 );
   (void)hipFree( ctx->d_kdig );
+  (void)hipFree( ctx->d_ktab ); (void)hipFree( ctx->d_arep ); (void)hipFree( ctx->d_ulist ); (void)hipFree( ctx->d_astat );
   (void)hipFree( ctx->d_P ); (void)hipFree( ctx->d_O ); (void)hipFree( ctx->d_blk ); (void)hipFree( ctx->d_slow );
   for( int i=0; i<5; i++ ) if( ctx->ev[i] ) (void)hipEventDestroy( ctx->ev[i] );
   for( int r=0; r<fdgpu_ed25519_ctx_t::NRING; r++ ) for( int i=0; i<5; i++ ) if( ctx->ring[r][i] ) (void)hipEventDestroy( ctx->ring[r][i] );
@@ -4336,6 +4550,15 @@ fdgpu_ed25519_slow_count( fdgpu_ed25519_ctx_t * ctx ) {
   if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return ~0UL;
   u32 cnt = 0u;
   if( hipMemcpy( &cnt, ctx->d_slow + ctx->max_sig, sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
+  return (unsigned long)cnt;
+}
+
+extern "C" unsigned long
+fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx ) {
+  if( !ctx || !ctx->half || !ctx->key_dedup || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0UL;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return ~0UL;
+  u32 cnt = 0u;
+  if( hipMemcpy( &cnt, ctx->d_slow + ctx->max_sig + 1, sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
   return (unsigned long)cnt;
 }
 

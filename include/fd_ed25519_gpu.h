@@ -382,6 +382,16 @@ fdgpu_ed25519_debug_fail_launch( fdgpu_ed25519_ctx_t * ctx, int on );
 unsigned long
 fdgpu_ed25519_slow_count( fdgpu_ed25519_ctx_t * ctx );
 
+/* Public keys the last batch launched on ctx decoded: on the half-size
+   throughput path each distinct key of a batch is decoded once (a key
+   that found no place in the batch's key table within its probes is
+   decoded once more; a malformed transaction's signatures count one
+   each; after a batch of nearly all distinct keys the next one looks
+   up only a sample of its keys and decodes the rest one by one).  0 when that batch took another path or the de-duplication is
+   off (fdgpu_debug_opts_t.key_dedup).  Waits for the batch. */
+unsigned long
+fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx );
+
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
                     unsigned long *       out_tags,
@@ -723,6 +733,10 @@ typedef struct fdgpu_debug_opts {
                                         also in verify tiles (whose default is on); 0: default */
   int           quad_sha;            /* latency path (half-size): 0 = default, the prep's hash role on a quad of lanes per
                                         signature up to 8,192 signatures (fd_sha512_RAM_quad); -1 = one lane (A/B) */
+  int           key_dedup;           /* half-size throughput path: 0 = default, each distinct public key of a batch is
+                                        decoded once (fd_keydedup_kernel); 1 = off, every signature decodes its own
+                                        key (A/B: exactly the kernels without it); 2 = TESTS, on with a 64-slot table
+                                        and two probes, so most keys fall back to being their own representative */
 } fdgpu_debug_opts_t;
 
 void
