@@ -21,7 +21,10 @@
      public key of the batch), fd_decode_kernel (roles by block: A and its
      table for the representatives, R and its table for every signature),
      fd_hashh_kernel (codes, SHA-512, the half-size scalars), then the walk
-     fd_dsmh_kernel (-A entries gathered at the representative's index)
+     fd_dsmh_kernel (-A entries gathered at the representative's index);
+     fd_keysplit_kernel orders the signatures of keys the batch
+     repeats ahead of the others, and those walk 64 doublings instead of 128
+     over the key's high tables [2^68](-A), [2^136](-A)
      fd_parse_kernel   (raw-payload batches) per transaction: fd_txn_parse,
                        fd_txn_t image, and the descriptor the kernels
                        above consume
@@ -134,6 +137,13 @@
 /* fd_keydedup_kernel: workgroups (of sg) whose lanes still look their keys up when the batch before had
    mostly distinct keys -- the sample that decides for the batch after */
 #define FD_KD_SBLK( sg ) ( (sg) >> 4 ? (sg) >> 4 : 1u )
+
+/* Repeated keys (fd_keysplit_kernel): a key with at least this many signatures in a batch is hot.  Its
+   two high tables cost about 0.7 of a cold walk (chains of 68 and 136 doublings, two 8-entry tables) and buy a
+   quarter of a walk per signature: break-even near 3 */
+#define FD_HOT_MIN 8u
+#define FD_KS_W    FD_LAT_SKEW_W     /* windows per part of a hot signature's c0 (fd_gpu_lattice.h) */
+#define FD_KS_NW   FD_LAT_SKEW_NW    /* windows stored for it: digA rows [0, 2 W + NW), digR rows [0, NW) */
 
 typedef signed char i8;
 
@@ -398,9 +408,14 @@ FD_DEV void sc_mul_5x8( u32 out[ 16 ], u32 const a[ 5 ], u32 const b[ 8 ] ) {
 /* k -> (c0, c1) with c0 == c1 k (mod 8l), re-checked here: mod 8 on the
    low words, mod l through sc_reduce (c0, |c1| k mod l < l); then
    s' = c1 S mod l.  0: no such pair within FD_LAT_BITS (full walk). */
-FD_DEV int hs_prepare( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 c0[ 5 ], u32 c1m[ 5 ], int & c1neg, u32 sp[ 8 ] ) {
-  int ng = 0;
-  if( !fd_lat_halfsize( c0, c1m, &ng, k ) ) return 0;
+/* HOT (a signature of a key the batch repeats): the skewed pair of fd_lat_skew, c0 of 7 words below
+   2^215 (still below l, so the same comparison), |c1| below 2^79. */
+template<int HOT = 0>
+FD_DEV int hs_prepare( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 c0[ HOT ? 7 : 5 ], u32 c1m[ 5 ], int & c1neg, u32 sp[ 8 ] ) {
+  constexpr int NC = HOT ? 7 : 5;
+  int ng = 0, nwin = 0;
+  if( HOT ) { if( !fd_lat_skew( c0, c1m, &ng, &nwin, k ) ) return 0; }
+  else if( !fd_lat_halfsize( c0, c1m, &ng, k ) ) return 0;
 #if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 4     /* timing only (wrong codes): ... up to the lattice reduction */
   return 0;
 #endif
@@ -413,12 +428,12 @@ FD_DEV int hs_prepare( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 c0[ 5 ], u32 c1m
   u32 diff = 0u;
   if( !ng ) {                                                          /* c0 == |c1| k */
 #pragma unroll
-    for( int i=0; i<8; i++ ) diff |= x[i] ^ ( i < 5 ? c0[i] : 0u );
+    for( int i=0; i<8; i++ ) diff |= x[i] ^ ( i < NC ? c0[i] : 0u );
   } else {                                                             /* c0 + |c1| k == 0 or l */
     u64 c = 0; u32 z = 0u, e = 0u;
 #pragma unroll
     for( int i=0; i<8; i++ ) {
-      u64 v = (u64)x[i] + (u64)( i < 5 ? c0[i] : 0u ) + c; c = v >> 32;
+      u64 v = (u64)x[i] + (u64)( i < NC ? c0[i] : 0u ) + c; c = v >> 32;
       z |= (u32)v; e |= (u32)v ^ lw[i];
     }
     diff = ( z != 0u ) & ( e != 0u );
@@ -475,6 +490,66 @@ FD_DEV void hs_store_digits( u32 const c0[ 5 ], u32 const c1m[ 5 ], int c1neg, u
     top = ( db && wb > top ) ? wb : top;
   }
   htop[s] = (unsigned char)top;                     /* highest window with a nonzero digit of c0, c1 or s' */
+}
+
+/* The window of the hot walk (fd_dsmh_kernel<.,1>) that adds s' digit j, radix 2^16: one base-point add in 16
+   of the windows 0..16, never two in one, from [0..32768] (2^e B):
+     j 0..4  at 4j        e = 0       j 9..12  at 4(j-9)+1   e = 140
+     j 5..8  at 4(j-5)+2  e = 72      j 13..15 at 4(j-13)+3  e = 196      (16 j = 4 window + e) */
+FD_DEV int hs_hot_bwin( int j ) { return j < 5 ? 4*j : j < 9 ? 4*(j-5) + 2 : j < 13 ? 4*(j-9) + 1 : 4*(j-13) + 3; }
+
+/* Digits of a hot signature's skewed pair at column col: c0's 2 W + NW signed radix-16 digits in digA's rows
+   (digit g belongs to part g / W -- [2^(68 part)](-A) -- and window g % W; the last part runs on to window
+   NW - 1), c1's NW digits in digR, s' as above; htop = the highest window with a nonzero digit of any. */
+FD_DEV void hs_store_digits_hot( u32 const c0[ 7 ], u32 const c1m[ 5 ], int c1neg, u32 const sp[ 8 ], u32 col, size_t n,
+                                 i8 * __restrict__ digA, i8 * __restrict__ digR, short * __restrict__ digB,
+                                 unsigned char * __restrict__ htop ) {
+  constexpr int NA = 2*FD_KS_W + FD_KS_NW;
+  int ca = 0, cr = 0, top = 0;
+  /* a word of c0 per round, not 54 unrolled digits: unrolled, their values and addresses stay live together
+     and cost the hash kernel its third wave (193 VGPRs against 167) */
+  u32 cw[ 7 ];
+#pragma unroll
+  for( int i=0; i<7; i++ ) cw[i] = c0[i];
+  i8 * pa = digA + col;
+#pragma unroll 1
+  for( int wd=0; wd<7; wd++ ) {
+    u32 x = cw[0];
+#pragma unroll
+    for( int i=0; i<6; i++ ) cw[i] = cw[i+1];
+#pragma unroll
+    for( int j=0; j<8; j++ ) {
+      int i = 8*wd + j;
+      if( i < NA ) {
+        int va = (int)( ( x >> (4*j) ) & 15u ) + ca;
+        ca = i < NA-1 ? ( va + 8 ) >> 4 : 0;        /* (c0 < 2^215: the top digit, kept as is, is <= 8) */
+        int da = va - ( ca << 4 );
+        *pa = (i8)da; pa += n;
+        int w = i < FD_KS_W ? i : i < 2*FD_KS_W ? i - FD_KS_W : i - 2*FD_KS_W;
+        top = ( da && w > top ) ? w : top;
+      }
+    }
+  }
+#pragma unroll
+  for( int i=0; i<FD_KS_NW; i++ ) {
+    int vr = (int)( ( c1m[i>>3] >> (4*(i&7)) ) & 15u ) + cr;
+    cr = i < FD_KS_NW-1 ? ( vr + 8 ) >> 4 : 0;      /* (|c1| < 2^79) */
+    int dr = vr - ( cr << 4 );
+    digR[(size_t)i*n + col] = (i8)( c1neg ? -dr : dr );
+    top = ( dr && i > top ) ? i : top;
+  }
+  int carry = 0;
+#pragma unroll
+  for( int i=0; i<FD_BDIG; i++ ) {
+    int bit = FD_BWIN*i;
+    int v = (int)((sp[bit>>5] >> (bit&31)) & ((1u<<FD_BWIN)-1u)) + carry;
+    carry = (v + (1<<(FD_BWIN-1))) >> FD_BWIN;
+    int db = v - (carry << FD_BWIN);
+    digB[(size_t)i*n + col] = (short)db;
+    int wb = hs_hot_bwin( i );                      /* htop counts the base-point windows too (test_gpu_hs_top.py) */
+    top = ( db && wb > top ) ? wb : top;
+  }
+  htop[col] = (unsigned char)top;
 }
 
 /* The wave's top window (half-size walks): the largest htop of its pending
@@ -591,13 +666,17 @@ fd_hash_kernel( unsigned char const *    __restrict__ payload,
 /* rc = 1 (throughput, after both decodes): the full result-code procedure
    first, and a slow signature is flagged in pstat; rc = 0 (fd_prep_kernel,
    beside the decodes): S's check only -- the DSM applies the rest. */
+/* KS (the batch partitioned into hot and cold signatures, fd_keysplit_kernel): digits, htop and the slow list's
+   entry go to column col, the signature's place in that order; a hot one (block-uniform) gets the skewed pair. */
+template<int KS = 0>
 FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
                        u32 const * __restrict__ map, u32 s, size_t n, int semantics, int rc,
                        unsigned char * __restrict__ pstat, i8 * __restrict__ code_out, i8 * __restrict__ digA,
                        i8 * __restrict__ digR, short * __restrict__ digB, u32 * __restrict__ slow,
                        u32 * __restrict__ slow_cnt, uint4 const * __restrict__ khash, u32 force_slow,
                        unsigned char * __restrict__ htop, u32 const * __restrict__ arep = (u32 const *)0,
-                       unsigned char const * __restrict__ astat = (unsigned char const *)0 ) {
+                       unsigned char const * __restrict__ astat = (unsigned char const *)0, u32 kcol = 0u, int hot = 0 ) {
+  u32 col = KS ? kcol : s;
   u32 m = map[s];
   u32 t = m & 0xffffffu, j = m >> 24;
   fdgpu_txn_desc_t d = desc[t];
@@ -633,15 +712,22 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
 #if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 5     /* timing only (wrong codes): ... up to s' (no digits) */
   { int ok = hs_prepare( k, Sw, c0, c1m, c1neg, sp ); code_out[s] = (i8)( ok + ( sp[0] & 1u ) + ( c0[0] & 1u ) ); return; }
 #endif
-  if( !( force_slow && s % force_slow == 0u ) && hs_prepare( k, Sw, c0, c1m, c1neg, sp ) ) {
-    hs_store_digits( c0, c1m, c1neg, sp, s, n, digA, digR, digB, htop );
+  if( KS && hot ) {
+    u32 c0h[7];
+    if( !( force_slow && s % force_slow == 0u ) && hs_prepare<1>( k, Sw, c0h, c1m, c1neg, sp ) ) {
+      hs_store_digits_hot( c0h, c1m, c1neg, sp, col, n, digA, digR, digB, htop );
+      code_out[s] = FD_ED25519_SUCCESS;
+      return;
+    }
+  } else if( !( force_slow && s % force_slow == 0u ) && hs_prepare( k, Sw, c0, c1m, c1neg, sp ) ) {
+    hs_store_digits( c0, c1m, c1neg, sp, col, n, digA, digR, digB, htop );
     code_out[s] = FD_ED25519_SUCCESS;
-  } else {
-    store_digits( k, Sw, s, n, digA, digB );
-    code_out[s] = FD_PEND_SLOW;
-    if( rc ) pstat[2*s] |= FD_PSTAT_SLOW;          /* fd_dsmh_kernel's half-size blocks skip it even once its code is final */
-    slow[ atomicAdd( slow_cnt, 1u ) ] = s;
+    return;
   }
+  store_digits( k, Sw, col, n, digA, digB );
+  code_out[s] = FD_PEND_SLOW;
+  if( rc ) pstat[2*s] |= FD_PSTAT_SLOW;            /* fd_dsmh_kernel's half-size blocks skip it even once its code is final */
+  slow[ atomicAdd( slow_cnt, 1u ) ] = col;
 }
 
 /* The latency path's hash role on a quad of lanes (fd_prep_kernel<.,1,1>): the S check and the loads on all
@@ -688,6 +774,53 @@ FD_DEV void hashh_one_q( unsigned char const * __restrict__ payload, fdgpu_txn_d
 #ifndef FD_HASHH_MINW
 #define FD_HASHH_MINW 0
 #endif
+/* Hot / cold order (fd_keysplit_kernel): the hot signatures fill order[] from the front, the cold ones from the
+   back, and the hash and walk kernels run one lane per place in it, in ceil(nh/256) hot blocks followed by the cold
+   blocks (at most sg + 1 in all), so a wave -- a whole block -- is all hot or all cold.  b: the block's index among
+   those.  Returns 0 for a lane beyond its part. */
+FD_DEV int ks_pos( u32 b, u32 nsig, u32 nh, u32 & col, int & hot ) {
+  u32 hb = ( nh + FD_WG - 1u ) / FD_WG;
+  hot = b < hb;
+  u32 j = ( hot ? b : b - hb ) * FD_WG + threadIdx.x;
+  col = hot ? j : nsig - 1u - j;
+  return j < ( hot ? nh : nsig - nh );
+}
+
+/* The high tables of hot key number hi: [1..8]( [2^(68 (part+1))](-A) ) in the -A table's entry format, at table
+   index 2 hi + part of htab, from the representative's canonical affine A */
+template<int FM = FD_CARRY_FOLD>
+FD_DEV void htab_build( uint4 * __restrict__ htab, u32 hi, u32 part, uint4 const * __restrict__ Axy, u32 rep ) {
+  uint4 const * ap = Axy + (size_t)rep*4;
+  ge_p3 A;
+  fe_from_quads( A.X, ap[0], ap[1] );
+  fe_from_quads( A.Y, ap[2], ap[3] );
+  A.Z = fe_one();
+  fe_neg( A.X, A.X ); fe_wcarry( A.X, A.X );              /* -A */
+  fe_mul<FM>( A.T, A.X, A.Y );
+  int nd = 4*FD_KS_W*( (int)part + 1 );
+#pragma unroll 1
+  for( int i=0; i<nd; i++ ) ge_p3_dbl<FM>( A, A );
+  u32 t = 2u*hi + part;
+  ge_cached c1;
+  ge_p3_to_cached<FM>( c1, A );
+  atab_store( htab, t, 1, c1 );
+#pragma unroll 1
+  for( int e=2; e<FD_ATAB_ENTRIES; e++ ) {
+    ge_p1p1 tt;
+    ge_add_cached<FM>( tt, A, c1 );
+    ge_p1p1_to_p3<FM>( A, tt );
+    /* the entry stored one element at a time: a whole ge_cached beside A, c1 and the sum costs the hash
+       kernel its third wave */
+    uint4 * b = htab + ((size_t)t * FD_ATAB_STORED + (size_t)( e - 1 )) * 8;
+    fe u;
+    fe_add( u, A.Y, A.X ); fe_store_packed( b + 0, u );
+    fe_sub( u, A.Y, A.X ); fe_store_packed( b + 2, u );
+    fe_store_packed( b + 4, A.Z );
+    fe d2 = fe_d2(); fe_mul<FM>( u, A.T, d2 ); fe_store_packed( b + 6, u );
+  }
+}
+
+template<int KS>
 #if FD_HASHH_MINW
 __global__ void __launch_bounds__( FD_WG, FD_HASHH_MINW )
 #else
@@ -709,7 +842,31 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  u32                                   force_slow,
                  unsigned char *          __restrict__ htop,
                  u32 const *              __restrict__ arep,
-                 unsigned char const *    __restrict__ astat ) {
+                 unsigned char const *    __restrict__ astat,
+                 /* KS (hot / cold partition, fd_keysplit_kernel): */
+                 u32 const *              __restrict__ order,    /* lane i of the walking blocks <-> signature order[i] */
+                 u32 const *              __restrict__ kscnt,    /* [0] hot keys, [1] hot signatures */
+                 u32 const *              __restrict__ hlist,    /* the hot keys' representatives */
+                 uint4 const *            __restrict__ Axy,
+                 uint4 *                  __restrict__ htab,     /* [hot key][2][8] entries: [1..8]([2^68](-A)), ([2^136](-A)) */
+                 u32                                   hblk ) {  /* blocks [0,hblk) build them: one lane per (key, part) */
+  if( KS ) {
+    if( blockIdx.x < hblk ) {
+      /* dispatched first, so the chains of 68 and 136 doublings run beside the hash and not after it.  A key that
+         does not decode or has small order builds nothing: its signatures' codes are final without a walk */
+      u32 i = blockIdx.x * FD_WG + threadIdx.x;
+      if( ( i >> 1 ) >= kscnt[0] ) return;
+      u32 rep = hlist[ i >> 1 ];
+      if( astat[rep] & 7u ) return;
+      htab_build<FD_TABLE_FM>( htab, i >> 1, i & 1u, Axy, rep );
+      return;
+    }
+    u32 col; int hot;
+    if( !ks_pos( blockIdx.x - hblk, nsig, kscnt[1], col, hot ) ) return;
+    hashh_one<1>( payload, desc, map, order[col], nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt,
+                  khash, force_slow, htop, arep, astat, col, hot );
+    return;
+  }
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
   hashh_one( payload, desc, map, s, nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt, khash,
@@ -907,11 +1064,13 @@ __device__ unsigned long long fd_clk_buf[ FD_CLK_BLOCKS ][ 4 ];
 template<int FM>
 FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 const * __restrict__ Rxy,
                      i8 const * __restrict__ digA, short const * __restrict__ digB, uint4 const * btab,
-                     i8 * __restrict__ code, u32 * __restrict__ Pbuf, int defer, u32 sa ) {   /* sa: whose -A table */
+                     i8 * __restrict__ code, u32 * __restrict__ Pbuf, int defer, u32 sa,      /* sa: whose -A table */
+                     u32 col ) {                                       /* col: the signature's digit column (s, or its
+                                                                          place in the hot / cold order) */
   ge_p3 P; ge_p3_identity( P );
   ge_p2 P2;
   atab_raw raw;
-  int da = digA[ (size_t)63*n + s ];
+  int da = digA[ (size_t)63*n + col ];
 
 #if FD_BWIN==16
   uint4 braw[6]; int db = 0;
@@ -923,7 +1082,7 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
 #endif
 #if FD_BWIN==16
     if( !(w & 3) ) {                                 /* base-point entry, also in flight */
-      db = digB[ (size_t)(w>>2)*n + s ];
+      db = digB[ (size_t)(w>>2)*n + col ];
       uint4 const * bp = btab + (size_t)( db < 0 ? -db : db )*6;
 #pragma unroll
       for( int i=0; i<6; i++ ) braw[i] = bp[i];
@@ -945,7 +1104,7 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
 #if FD_BWIN==8
     if( !(w & 1) ) {
       ge_p1p1_to_p3<FM>( P, t );
-      int db = digB[ (size_t)(w>>1)*n + s ];
+      int db = digB[ (size_t)(w>>1)*n + col ];
       int e = db < 0 ? -db : db;
       uint4 const * bp = btab + e*6;
       ge_precomp bq;
@@ -967,7 +1126,7 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
     }
 #endif
     ge_p1p1_to_p2<FM>( P2, t );
-    if( w > 0 ) da = digA[ (size_t)(w-1)*n + s ];
+    if( w > 0 ) da = digA[ (size_t)(w-1)*n + col ];
   }
 
   if( defer ) {
@@ -1014,7 +1173,7 @@ fd_dsm_kernel( u32                      nsig,
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
   if( code[s] != FD_ED25519_SUCCESS ) return;
-  dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, Pbuf, defer, s );
+  dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, Pbuf, defer, s, s );
   FD_CLK_END
 }
 
@@ -1028,9 +1187,13 @@ __global__ void __launch_bounds__( FD_WG )
 fd_dsm_slow_kernel( u32 nsig, uint4 const * __restrict__ tab, uint4 const * __restrict__ Rxy,
                     i8 const * __restrict__ digA, short const * __restrict__ digB, uint4 const * __restrict__ btab,
                     i8 * __restrict__ code, u32 const * __restrict__ slow, u32 const * __restrict__ slow_cnt,
-                    u32 first, u32 const * __restrict__ arep ) {
+                    u32 first, u32 const * __restrict__ arep, u32 const * __restrict__ order ) {
   u32 i = first + blockIdx.x * FD_WG + threadIdx.x;
-  if( i < *slow_cnt ) { u32 s = slow[i]; dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[s] : s ); }
+  /* order (hot / cold partition, fd_keysplit_kernel): the list names digit columns, order[] the signature */
+  if( i < *slow_cnt ) {
+    u32 col = slow[i], s = order ? order[col] : col;
+    dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[s] : s, col );
+  }
 }
 
 /* Latency half-size path: the slow list after the walks, the result-code
@@ -1048,7 +1211,7 @@ FD_DEV void slowl_tail( u32 nsig, uint4 const * __restrict__ tab, uint4 const * 
     if( code[s] != FD_PEND_SLOW ) continue;
     int c = result_code( FD_ED25519_SUCCESS, pstat[2*s], pstat[2*s+1], semantics, 0 );
     if( c != FD_ED25519_SUCCESS ) { code[s] = (i8)c; continue; }
-    dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, s );
+    dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, (u32 *)0, 0, s, s );
   }
 }
 
@@ -1092,7 +1255,69 @@ fd_tableh_kernel( u32 nsig, u32 sg, i8 const * __restrict__ code, uint4 const * 
 #ifndef FD_DSMH_LDS
 #define FD_DSMH_LDS 0
 #endif
+/* The walk of a hot signature (a key the batch repeats): c0 in three parts of W = 17 windows,
+     Q = [s']B + [c0_0](-A) + [c0_1]([2^68](-A)) + [c0_2]([2^136](-A)) + [c1](-R),
+   over 17 windows (up to FD_KS_NW when a lane's pair needs them) = 64 doublings.  Per window: 4 doublings, the
+   three -A-part adds (part 0 from the key's -A table at sa, parts 1 and 2 from its high tables at 2 hi, 2 hi + 1
+   of htab), the -R add, and s' digit j from btab / btabh at window hs_hot_bwin( j ).  Each gather is issued one
+   add ahead, so two raw entries are live at a time, as in the cold walk. */
 template<int FM>
+FD_DEV int dsmh_hot( u32 s, u32 col, size_t n, int wtop, u32 sa, u32 hi,
+                     uint4 const * __restrict__ tabA, uint4 const * __restrict__ tabR, uint4 const * __restrict__ htab,
+                     i8 const * __restrict__ digA, i8 const * __restrict__ digR, short const * __restrict__ digB,
+                     uint4 const * __restrict__ btab, uint4 const * __restrict__ btabh ) {
+  ge_p3 P; ge_p3_identity( P );
+  ge_p2 P2;
+  atab_raw ra, rb;
+  i8 const * dA = digA + col;
+  /* parts 0 and 1 end at window W - 1: above it only part 2 and c1 have digits */
+  int d2 = dA[ (size_t)( 2*FD_KS_W + wtop )*n ], dr = digR[ (size_t)wtop*n + col ];
+  int d0 = wtop < FD_KS_W ? (int)dA[ (size_t)wtop*n ] : 0, d1 = wtop < FD_KS_W ? (int)dA[ (size_t)( FD_KS_W + wtop )*n ] : 0;
+#pragma unroll 1
+  for( int w=wtop; w>=0; w-- ) {
+    atab_fetch( ra, htab, 2u*hi + 1u, d2 < 0 ? -d2 : d2 );   /* in flight during the doublings */
+    ge_p1p1 t;
+    if( w != wtop ) {
+#pragma unroll 1
+      for( int r=0; r<3; r++ ) { ge_dbl<FM>( t, P2 ); ge_p1p1_to_p2<FM>( P2, t ); }
+      ge_dbl<FM>( t, P2 ); ge_p1p1_to_p3<FM>( P, t );
+    }
+    atab_fetch( rb, htab, 2u*hi, d1 < 0 ? -d1 : d1 );
+    { ge_cached q; atab_unpack( q, ra ); ge_cached_cneg( q, d2 < 0 ); ge_add_cached<FM>( t, P, q ); ge_p1p1_to_p3<FM>( P, t ); }
+    atab_fetch( ra, tabA, sa, d0 < 0 ? -d0 : d0 );
+    { ge_cached q; atab_unpack( q, rb ); ge_cached_cneg( q, d1 < 0 ); ge_add_cached<FM>( t, P, q ); ge_p1p1_to_p3<FM>( P, t ); }
+    atab_fetch( rb, tabR, s, dr < 0 ? -dr : dr );
+    { ge_cached q; atab_unpack( q, ra ); ge_cached_cneg( q, d0 < 0 ); ge_add_cached<FM>( t, P, q ); ge_p1p1_to_p3<FM>( P, t ); }
+    /* s' digit: class w & 3 picks the table, (w >> 2) the digit within its run */
+    int cl = w & 3;
+    int bw = w <= ( cl==0 ? 16 : cl==2 ? 14 : cl==1 ? 13 : 11 );
+    int db = bw ? digB[ (size_t)( ( cl==0 ? 0 : cl==2 ? 5 : cl==1 ? 9 : 13 ) + ( w >> 2 ) )*n + col ] : 0;
+    { ge_cached q; atab_unpack( q, rb ); ge_cached_cneg( q, dr < 0 ); ge_add_cached<FM>( t, P, q ); }
+    if( bw ) {
+      uint4 braw[6];
+      uint4 const * bt = cl==0 ? btab : btabh + (size_t)( cl==2 ? 0 : cl==1 ? 1 : 2 ) * ( (size_t)FD_BTAB_ENTRIES * 6 );
+      uint4 const * bp = bt + (size_t)( db < 0 ? -db : db )*6;
+#pragma unroll
+      for( int i=0; i<6; i++ ) braw[i] = bp[i];
+      ge_precomp bq;
+      ge_p1p1_to_p3<FM>( P, t );
+      fe_from_quads( bq.ypx,  braw[0], braw[1] );
+      fe_from_quads( bq.ymx,  braw[2], braw[3] );
+      fe_from_quads( bq.xy2d, braw[4], braw[5] );
+      ge_precomp_cneg( bq, db < 0 );
+      ge_add_precomp<FM>( t, P, bq );
+    }
+    ge_p1p1_to_p2<FM>( P2, t );
+    if( w > 0 ) {
+      int lo = w - 1 < FD_KS_W;
+      d2 = dA[ (size_t)( 2*FD_KS_W + w - 1 )*n ]; dr = digR[ (size_t)( w - 1 )*n + col ];
+      d0 = lo ? (int)dA[ (size_t)( w - 1 )*n ] : 0; d1 = lo ? (int)dA[ (size_t)( FD_KS_W + w - 1 )*n ] : 0;
+    }
+  }
+  return fe_is_zero( P2.X ) & fe_eq( P2.Y, P2.Z );
+}
+
+template<int FM, int KS = 0>
 __global__ void __launch_bounds__( FD_WG, FM ? FD_DSMH_MINW : 1 )
 fd_dsmh_kernel( u32                      nsig,
                 uint4 const * __restrict__ tabA,
@@ -1111,34 +1336,51 @@ fd_dsmh_kernel( u32                      nsig,
                 unsigned char const * __restrict__ htop,
                 int                        rc,
                 int                        semantics,
-                u32 const *   __restrict__ arep ) {      /* keys de-duplicated: -A's table is at arep[s], else NULL */
+                u32 const *   __restrict__ arep,         /* keys de-duplicated: -A's table is at arep[s], else NULL */
+                /* KS (hot / cold partition, fd_keysplit_kernel; the grid is nslowblk + sg + 1 blocks): */
+                u32 const *   __restrict__ order,        /* lane i of the walking blocks <-> signature order[i] */
+                u32 const *   __restrict__ kscnt,        /* [1] hot signatures */
+                u32 const *   __restrict__ hidx,         /* a hot representative's dense index */
+                uint4 const * __restrict__ htab,         /* the high tables (htab_build) */
+                uint4 const * __restrict__ btabh ) {     /* [0..32768](2^e B), e = 72, 140, 196 */
   size_t n = nsig;
   if( blockIdx.x < nslowblk ) {
     /* the first blocks take the head of the slow list (full 253-bit walk,
        about twice a half-size walk): dispatched first, they run beside the
        half-size waves instead of after them; fd_dsm_slow_kernel takes the rest */
     u32 i = blockIdx.x * FD_WG + threadIdx.x;
-    if( i < *slow_cnt ) { u32 ss = slow[i]; dsm_one<FM>( ss, n, tabA, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[ss] : ss ); }
+    if( i < *slow_cnt ) {
+      u32 cs = slow[i], ss = KS ? order[cs] : cs;
+      dsm_one<FM>( ss, n, tabA, Rxy, digA, digB, btab, code, (u32 *)0, 0, arep ? arep[ss] : ss, cs );
+    }
     return;
   }
-  u32 s = ( blockIdx.x - nslowblk ) * FD_WG + threadIdx.x;
+  /* col: the lane's digit column -- the signature itself, or (KS) its place in the hot / cold order */
+  u32 s, col; int in, hot = 0;
+  if( KS ) { in = ks_pos( blockIdx.x - nslowblk, nsig, kscnt[1], col, hot ); s = in ? order[col] : 0u; }
+  else { s = col = ( blockIdx.x - nslowblk ) * FD_WG + threadIdx.x; in = s < nsig; }
   /* a slow-list signature's code may already be final (SUCCESS) when this
      block starts: the flag, not the code, keeps it out */
   /* rc (latency path, after fd_prep_kernel): the result-code procedure
      here; slow signatures (FD_PEND_SLOW) are left to fd_dsm_slowl_kernel */
-  int c = s < nsig ? (int)code[s] : FD_ED25519_ERR_SIG;
-  if( rc && s < nsig ) c = result_code( c, pstat[2*s], pstat[2*s+1], semantics, 0 );
+  int c = in ? (int)code[s] : FD_ED25519_ERR_SIG;
+  if( rc && in ) c = result_code( c, pstat[2*s], pstat[2*s+1], semantics, 0 );
   int pend = c == FD_ED25519_SUCCESS && !( pstat[2*s] & FD_PSTAT_SLOW );
   /* the walk starts at the wave's highest nonzero window of c0, c1 and s' (31-32 unless a lane's
      scalar exceeds 2^131; window 30 or above while s' >= 2^240): every lane of the wave is still here */
-  int wtop = hs_wave_top( pend, htop, s );
-  if( !pend ) { if( rc && s < nsig && c != FD_PEND_SLOW ) code[s] = (i8)c; return; }
+  int wtop = hs_wave_top( pend, htop, col );
+  if( !pend ) { if( rc && in && c != FD_PEND_SLOW ) code[s] = (i8)c; return; }
+  u32 sa = arep ? arep[s] : s;
+  if( KS && hot ) {                                     /* (block-uniform) */
+    int ok = dsmh_hot<FM>( s, col, n, wtop, sa, hidx[sa], tabA, tabR, htab, digA, digR, digB, btab, btabh );
+    code[s] = ok ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
+    return;
+  }
   FD_CLK_BEGIN
   ge_p3 P; ge_p3_identity( P );
   ge_p2 P2;
   atab_raw ra, rr;
-  u32 sa = arep ? arep[s] : s;
-  int da = digA[ (size_t)wtop*n + s ], dr = digR[ (size_t)wtop*n + s ];
+  int da = digA[ (size_t)wtop*n + col ], dr = digR[ (size_t)wtop*n + col ];
 #pragma unroll 1
   for( int w=wtop; w>=0; w-- ) {
     atab_fetch( ra, tabA, sa, da < 0 ? -da : da );    /* in flight during the doublings */
@@ -1160,7 +1402,7 @@ fd_dsmh_kernel( u32                      nsig,
        digit j+8 (bits 16j+128..) at window 4j+2 from [0..32768](2^120 B):
        one base-point add per even window */
     int bw = !(w & 1) && w < 32;
-    int db = bw ? digB[ (size_t)( (w>>2) + ( (w & 2) ? 8 : 0 ) )*n + s ] : 0;
+    int db = bw ? digB[ (size_t)( (w>>2) + ( (w & 2) ? 8 : 0 ) )*n + col ] : 0;
     {
       ge_cached q; atab_unpack( q, rr ); ge_cached_cneg( q, dr < 0 );
       ge_add_cached<FM>( t, P, q );
@@ -1180,7 +1422,7 @@ fd_dsmh_kernel( u32                      nsig,
       ge_add_precomp<FM>( t, P, bq );
     }
     ge_p1p1_to_p2<FM>( P2, t );
-    if( w > 0 ) { da = digA[ (size_t)(w-1)*n + s ]; dr = digR[ (size_t)(w-1)*n + s ]; }
+    if( w > 0 ) { da = digA[ (size_t)(w-1)*n + col ]; dr = digR[ (size_t)(w-1)*n + col ]; }
   }
   /* Q == O: X == 0 and Y == Z (Z != 0: complete formulas) */
   int ok = fe_is_zero( P2.X ) & fe_eq( P2.Y, P2.Z );
@@ -2140,6 +2382,7 @@ FD_DEV u64 fd_xxh64_64( u64 seed, unsigned char const * p ) {
    Which of a key's signatures wins its slot differs from run to run; every one of them gives the same
    point, status and table. */
 #define FD_KD_PROBES 16u
+template<int KS>
 __global__ void __launch_bounds__( FD_WG )
 fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
                     fdgpu_txn_desc_t const * __restrict__ desc,
@@ -2153,9 +2396,17 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
                     u32 *                    __restrict__ ulist,
                     u32 *                    __restrict__ ucnt,
                     unsigned char *          __restrict__ pstat,
-                    u32                                   sblk ) {
+                    u32                                   sblk,
+                    /* KS: the signatures per key, counted at the representative up to hot_min (launch_batch zeroes
+                       kcnt[0, nsig) ahead): a plain read first and a no-return add only while below the bound, so
+                       one key with a million signatures does not serialise a million atomics on one word.  The
+                       bypass counts nothing: no hot keys then.  Also zeroes fd_keysplit_kernel's three counters,
+                       ucnt[3..5]. */
+                    u32 *                    __restrict__ kcnt,
+                    u32                                   hot_min ) {
   __shared__ u32 wcnt[ FD_WG / 64 + 1 ];
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
+  if( KS && !s ) { ucnt[3] = 0u; ucnt[4] = 0u; ucnt[5] = 0u; }
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
   int peek = !bypass;
   int own = s < nsig;
@@ -2192,6 +2443,10 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
         for( int k=0; k<8; k++ ) diff |= w[k] ^ wc[k];
         if( !diff ) { rep = c; own = 0; break; }
       }
+      if( KS && !bypass ) {
+        u32 * kc = kcnt + rep;
+        if( __hip_atomic_load( kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP ) < hot_min ) atomicAdd( kc, 1u );
+      }
     }
     arep[s] = rep;
   }
@@ -2222,6 +2477,45 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
     if( bypass && blockIdx.x >= sblk ) ulist[ s - nsamp ] = s;
     else ulist[ wcnt[ FD_WG/64 ] + wcnt[wv] + (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) ) ] = s;
   }
+}
+
+/* Repeated keys, after fd_keydedup_kernel, one lane per signature.  A key is hot when its count
+   reached hot_min; a signature is hot when its key is.
+     hidx[rep], hlist[]  the hot representatives get a dense index (at most nsig / hot_min of them, which sizes
+                         the high tables) and are listed by it;
+     order[]             the hot signatures from the front, the cold ones (and the lanes of malformed
+                         transactions) from the back: fd_hashh_kernel and fd_dsmh_kernel then run lane i <->
+                         signature order[i] (ks_pos);
+     cnt[0..2]           hot keys, hot signatures, cold signatures (zeroed by fd_keydedup_kernel).
+   A ballot per wave, the waves' counts summed in LDS, one atomic add per workgroup and list, as ulist.  No lane
+   reads what another lane of this launch writes. */
+__global__ void __launch_bounds__( FD_WG )
+fd_keysplit_kernel( u32 nsig, u32 const * __restrict__ arep, u32 const * __restrict__ kcnt, u32 hot_min,
+                    u32 * __restrict__ hidx, u32 * __restrict__ hlist, u32 * __restrict__ order, u32 * __restrict__ cnt,
+                    u32 hcap ) {
+  __shared__ u32 wc[ 3 ][ FD_WG / 64 ], base[ 3 ];
+  u32 s = blockIdx.x * FD_WG + threadIdx.x;
+  int in = s < nsig;
+  u32 rep = in ? arep[s] : 0u;
+  int hot = in && kcnt[rep] >= hot_min;
+  int f[ 3 ] = { hot && rep == s, hot, in && !hot };
+  u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, rank[ 3 ];
+#pragma unroll
+  for( int k=0; k<3; k++ ) {
+    unsigned long long mk = __ballot( f[k] );
+    if( !lane ) wc[k][wv] = (u32)__popcll( mk );
+    rank[k] = (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) );
+  }
+  __syncthreads();
+  if( threadIdx.x < 3u ) {
+    u32 k = threadIdx.x, tot = 0u;
+    for( u32 w=0; w<FD_WG/64; w++ ) { u32 c = wc[k][w]; wc[k][w] = tot; tot += c; }
+    base[k] = tot ? atomicAdd( cnt + k, tot ) : 0u;
+  }
+  __syncthreads();
+  if( f[0] ) { u32 i = base[0] + wc[0][wv] + rank[0]; if( i < hcap ) { hidx[s] = i; hlist[i] = s; } }
+  if( f[1] ) order[ base[1] + wc[1][wv] + rank[1] ] = s;
+  if( f[2] ) order[ nsig - 1u - ( base[2] + wc[2][wv] + rank[2] ) ] = s;
 }
 
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
@@ -2560,6 +2854,16 @@ struct fdgpu_ed25519_ctx {
   u32 *   d_arep;                /*   [max_sig] each signature's representative */
   u32 *   d_ulist;               /*   [max_sig] the representatives + their count */
   unsigned char * d_astat;       /*   [max_sig] A's status, at the representative's index */
+  int     key_split;             /* ... and the signatures of repeated keys walk 64 doublings: the resolved
+                                    choice, 1 = on (needs key_dedup), 0 = off */
+  u32     hot_min;               /*   signatures that make a key hot (FD_HOT_MIN; fdgpu_debug_opts_t.key_split = 2: 2) */
+  u32     hot_cap;               /*   max_sig / hot_min: the most hot keys a batch can hold */
+  u32 *   d_kcnt;                /*   [max_sig] signatures per key, at the representative, saturating */
+  u32 *   d_hidx;                /*   [max_sig] a hot representative's dense index */
+  u32 *   d_hlist;               /*   [hot_cap] the hot representatives */
+  u32 *   d_order;               /*   [max_sig] hot signatures from the front, cold from the back */
+  uint4 * d_htab;                /*   [hot_cap][2][8][8] the high tables, 2 KB per hot key */
+  uint4 * d_btabh;               /*   [3][FD_BTAB_ENTRIES][6] [0..32768](2^e B), e = 72, 140, 196 */
   hipEvent_t ev[5];
   enum { NRING = 64 };
   hipEvent_t ring[ NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
@@ -2808,9 +3112,19 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
         u32 slots = 64u;
         if( !ctx->kd_tiny ) while( slots < ctx->kd_slots && slots < 2u*nsig ) slots <<= 1;
         HIPCHK( hipMemsetAsync( ctx->d_ktab, 0, (size_t)slots * sizeof(u32), st ), -3 );
-        hipLaunchKernelGGL( fd_keydedup_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
+        if( ctx->key_split ) {
+          /* repeated keys: count the signatures per key, then partition the batch into hot and cold */
+          HIPCHK( hipMemsetAsync( ctx->d_kcnt, 0, (size_t)nsig * sizeof(u32), st ), -3 );
+          hipLaunchKernelGGL( fd_keydedup_kernel<1>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
+                              ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep, ctx->d_ulist,
+                              ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ), ctx->d_kcnt, ctx->hot_min );
+          hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
+                              (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
+                              ctx->d_slow + ctx->max_sig + 4, ctx->hot_cap );
+        } else
+        hipLaunchKernelGGL( fd_keydedup_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
                             ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep, ctx->d_ulist,
-                            ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ) );
+                            ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ), (u32 *)NULL, 0u );
         hipLaunchKernelGGL( fd_decode_kernel, dim3(2*sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
                             ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR, (u32 const *)ctx->d_ulist,
                             ctx->d_slow + ctx->max_sig + 1, ctx->d_astat, (u32)sg );
@@ -2829,11 +3143,23 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
         hipLaunchKernelGGL( fd_sha_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, ctx->d_kdig );
         kh = ctx->d_kdig;
       }
-      hipLaunchKernelGGL( fd_hashh_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
+      if( ctx->key_split ) {
+        /* the high tables of the hot keys in the first blocks (two lanes per key, the worst case of nsig / hot_min
+           keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
+        unsigned hb = (unsigned)( ( 2UL * ( sig_cnt / ctx->hot_min ) + FD_WG - 1 ) / FD_WG );
+        hipLaunchKernelGGL( fd_hashh_kernel<1>, dim3(hb + sg + 1), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
+                            ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_slow,
+                            ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop,
+                            (u32 const *)ctx->d_arep, (unsigned char const *)ctx->d_astat, (u32 const *)ctx->d_order,
+                            (u32 const *)( ctx->d_slow + ctx->max_sig + 4 ), (u32 const *)ctx->d_hlist,
+                            (uint4 const *)ctx->d_Axy, ctx->d_htab, (u32)hb );
+      } else
+      hipLaunchKernelGGL( fd_hashh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
                           ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_slow,
                           ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop,
                           (u32 const *)( ctx->key_dedup ? ctx->d_arep : NULL ),
-                          (unsigned char const *)( ctx->key_dedup ? ctx->d_astat : NULL ) );
+                          (unsigned char const *)( ctx->key_dedup ? ctx->d_astat : NULL ), (u32 const *)NULL,
+                          (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 *)NULL, 0u );
 #if !FD_HALF_FUSED_TABLE
       hipLaunchKernelGGL( fd_tableh_kernel, dim3(2*sg), dim3(FD_WG), 0, st, nsig, (u32)sg, code, ctx->d_Axy, ctx->d_Rxy,
                           ctx->d_tab, ctx->d_tabR );
@@ -2868,28 +3194,30 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
     else if( hs )                              /* one lane: the half-size walk, result codes at its start */
       hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                           ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow,
-                          ctx->d_slow + ctx->max_sig, 0u, ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL );
+                          ctx->d_slow + ctx->max_sig, 0u, ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL,
+                          (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL );
     else if( half ) {
       /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the
          rest (if any) in fd_dsm_slow_kernel */
       unsigned nsb = ( sg + 63u ) / 64u;
       u32 * slow_cnt = ctx->d_slow + ctx->max_sig;
       u32 const * arep = ctx->key_dedup ? ctx->d_arep : NULL;     /* -A's tables at the representatives */
-      if( nsig <= ctx->nofold_max ) {
-        hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(nsb + sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
-                            ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
-                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep );
-        if( ctx->timing ) hipEventRecord( ev[2], st );
-        hipLaunchKernelGGL( fd_dsm_slow_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
-                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG, arep );
-      } else {
-        hipLaunchKernelGGL( fd_dsmh_kernel<1>, dim3(nsb + sg), dim3(FD_WG), FD_DSMH_LDS, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
-                            ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
-                            ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep );
-        if( ctx->timing ) hipEventRecord( ev[2], st );
-        hipLaunchKernelGGL( fd_dsm_slow_kernel<1>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
-                            ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, nsb * FD_WG, arep );
-      }
+      /* repeated keys: lane i <-> signature order[i], hot blocks then cold blocks (at most sg + 1 of them) */
+      int ks = ctx->key_split;
+      u32 const * order = ks ? ctx->d_order : NULL, * kscnt = ks ? ctx->d_slow + ctx->max_sig + 4 : NULL;
+      u32 const * hidx = ks ? ctx->d_hidx : NULL;
+      uint4 const * htab = ks ? ctx->d_htab : NULL, * btabh = ks ? ctx->d_btabh : NULL;
+      unsigned wg = nsb + sg + ( ks ? 1u : 0u );
+      int fold = nsig > ctx->nofold_max;
+      hipLaunchKernelGGL( ( fold ? ( ks ? fd_dsmh_kernel<1,1> : fd_dsmh_kernel<1,0> )
+                                 : ( ks ? fd_dsmh_kernel<0,1> : fd_dsmh_kernel<0,0> ) ),
+                          dim3(wg), dim3(FD_WG), fold ? FD_DSMH_LDS : 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
+                          ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
+                          ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep, order, kscnt, hidx, htab, btabh );
+      if( ctx->timing ) hipEventRecord( ev[2], st );
+      hipLaunchKernelGGL( ( fold ? fd_dsm_slow_kernel<1> : fd_dsm_slow_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, nsig,
+                          ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt,
+                          nsb * FD_WG, arep, order );
     }
     else if( nsig <= ctx->nofold_max )         /* <= 2 waves per SIMD: latency-bound, independent column chains */
       hipLaunchKernelGGL( fd_dsm_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy,
@@ -2925,14 +3253,14 @@ static void launcher_drain( fdgpu_launcher_t * L );
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
 fdgpu_debug_set_opts( fdgpu_debug_opts_t const * opts ) {
   std::lock_guard<std::mutex> lk( g_dbg_mu );
   if( opts ) g_dbg = *opts;
-  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0 };
+  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0 };
 }
 
 /* staging + device buffers of async slot i (once) */
@@ -2999,10 +3327,11 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   HIPCHK( hipMalloc( &ctx->d_P, ns * 30 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_O, ns * 10 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_blk, ( ( ns + FD_WG - 1 ) / FD_WG ) * 10 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + 4 ) * sizeof(u32) ), -1 );   /* + the slow count, the distinct-key count, whether
-                                                                           most keys of the last batch were distinct, and the
-                                                                           sample's count (fd_keydedup_kernel) */
-  HIPCHK( hipMemsetAsync( ctx->d_slow + ns, 0, 4 * sizeof(u32), ctx->stream ), -1 );
+  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + 8 ) * sizeof(u32) ), -1 );   /* + the slow count, the distinct-key count, whether
+                                                                           most keys of the last batch were distinct, the
+                                                                           sample's count (fd_keydedup_kernel), and the hot
+                                                                           keys, hot and cold signatures (fd_keysplit_kernel) */
+  HIPCHK( hipMemsetAsync( ctx->d_slow + ns, 0, 8 * sizeof(u32), ctx->stream ), -1 );
   fdgpu_debug_opts_t dbg; debug_opts_get( &dbg );   /* test / A/B choices (fdgpu_debug_set_opts), never the environment */
   ctx->half = dbg.half >= 0 ? dbg.half : FD_HALF;
   ctx->half_force_slow = dbg.half_force_slow;
@@ -3023,6 +3352,19 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
       HIPCHK( hipMalloc( &ctx->d_arep, ns * sizeof(u32) ), -1 );
       HIPCHK( hipMalloc( &ctx->d_ulist, ns * sizeof(u32) ), -1 );
       HIPCHK( hipMalloc( &ctx->d_astat, ns ), -1 );
+      /* the signatures of repeated keys walk 64 doublings (fd_keysplit_kernel) */
+      ctx->key_split = dbg.key_split != 1;
+      if( ctx->key_split ) {
+        ctx->hot_min = dbg.key_split == 2 ? 2u : FD_HOT_MIN;
+        ctx->hot_cap = (u32)( ns / ctx->hot_min );
+        size_t hc = ctx->hot_cap ? ctx->hot_cap : 1UL;
+        HIPCHK( hipMalloc( &ctx->d_kcnt, ns * sizeof(u32) ), -1 );
+        HIPCHK( hipMalloc( &ctx->d_hidx, ns * sizeof(u32) ), -1 );
+        HIPCHK( hipMalloc( &ctx->d_hlist, hc * sizeof(u32) ), -1 );
+        HIPCHK( hipMalloc( &ctx->d_order, ns * sizeof(u32) ), -1 );
+        HIPCHK( hipMalloc( &ctx->d_htab, hc * 2 * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
+        HIPCHK( hipMalloc( &ctx->d_btabh, (size_t)3 * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+      }
     }
   }
   ctx->small_max  = dbg.small_batch_max >= 0 ? (unsigned long)dbg.small_batch_max : FD_SMALL_BATCH_MAX;
@@ -3039,6 +3381,12 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream, ctx->d_btab, 0 );
   if( ctx->half )
     hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream, ctx->d_btab2, 120 );
+  if( ctx->key_split ) {
+    int const e[ 3 ] = { 72, 140, 196 };               /* the hot walk's s' digits 5-8, 9-12, 13-15 (hs_hot_bwin) */
+    for( int t=0; t<3; t++ )
+      hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream,
+                          ctx->d_btabh + (size_t)t * FD_BTAB_ENTRIES * 6, e[t] );
+  }
   HIPCHK( hipGetLastError(), -1 );
   for( int i=0; i<fdgpu_ed25519_ctx_t::NSLOT; i++ ) HIPCHK( hipEventCreateWithFlags( &ctx->slot[i].done, hipEventDisableTiming ), -1 );
   HIPCHK( hipHostMalloc( (void **)&ctx->h_flag, ( fdgpu_ed25519_ctx_t::NSLOT + 2 ) * sizeof(unsigned long), hipHostMallocDefault ), -1 );
@@ -3093,6 +3441,8 @@ fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx ) {
   (void)hipFree( ctx->d_tabR ); (void)hipFree( ctx->d_digR ); (void)hipFree( ctx->d_htop ); (void)hipFree( ctx->d_btab2 );
   (void)hipFree( ctx->d_kdig );
   (void)hipFree( ctx->d_ktab ); (void)hipFree( ctx->d_arep ); (void)hipFree( ctx->d_ulist ); (void)hipFree( ctx->d_astat );
+  (void)hipFree( ctx->d_kcnt ); (void)hipFree( ctx->d_hidx ); (void)hipFree( ctx->d_hlist ); (void)hipFree( ctx->d_order );
+  (void)hipFree( ctx->d_htab ); (void)hipFree( ctx->d_btabh );
   (void)hipFree( ctx->d_P ); (void)hipFree( ctx->d_O ); (void)hipFree( ctx->d_blk ); (void)hipFree( ctx->d_slow );
   for( int i=0; i<5; i++ ) if( ctx->ev[i] ) (void)hipEventDestroy( ctx->ev[i] );
   for( int r=0; r<fdgpu_ed25519_ctx_t::NRING; r++ ) for( int i=0; i<5; i++ ) if( ctx->ring[r][i] ) (void)hipEventDestroy( ctx->ring[r][i] );
@@ -4560,6 +4910,19 @@ fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx ) {
   u32 cnt = 0u;
   if( hipMemcpy( &cnt, ctx->d_slow + ctx->max_sig + 1, sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
   return (unsigned long)cnt;
+}
+
+extern "C" int
+fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, unsigned long * hot_sigs ) {
+  if( hot_keys ) *hot_keys = 0UL;
+  if( hot_sigs ) *hot_sigs = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_split || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 2 ] = { 0u, 0u };
+  if( hipMemcpy( cnt, ctx->d_slow + ctx->max_sig + 4, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( hot_keys ) *hot_keys = (unsigned long)cnt[0];
+  if( hot_sigs ) *hot_sigs = (unsigned long)cnt[1];
+  return 0;
 }
 
 extern "C" unsigned long

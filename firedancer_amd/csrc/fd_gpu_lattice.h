@@ -247,3 +247,130 @@ FD_LAT_FN int fd_lat_halfsize( uint32_t c0[ 5 ], uint32_t c1m[ 5 ], int * c1neg,
   uint32_t lim = 1u << ( FD_LAT_BITS - 128 );
   return ( c0[4] < lim ) & ( c1m[4] < lim ) & (int)( c1m[0] & 1u );
 }
+
+/* ---- skewed pair, for the signatures of a public key the batch repeats ----
+
+   The lattice fixes |c0| |c1| ~ 8l, not the balance.  The walk's doublings follow the longer scalar, and
+   [c1](-R) is per signature, but for a key with many signatures [2^(4W)](-A) and [2^(8W)](-A) are built
+   once per key, so c0 may be three times as long as c1 at no cost in doublings:
+
+     c0 = c0_0 + 2^(4W) c0_1 + 2^(8W) c0_2,   W = FD_LAT_SKEW_W = 17
+     Q  = [s']B + sum_p [c0_p]( [2^(4Wp)](-A) ) + [c1](-R)            (an identity for every A)
+
+   with the same conditions as above: c0 == c1 k (mod 8l), c1 odd, 0 < |c1| < l.  Same Euclid, stopped at the
+   first remainder below 2^T, T = 188: its cofactor is below 8l / 2^188 < 2^67, which 17 signed radix-16
+   digits hold, and the remainder's 47 digits fit the three parts with room to spare -- room the candidates
+   below need when that cofactor is even.
+
+   A pair needs fd_lat_skew_windows windows: v < 2^(4d-1) has d signed digits in [-8,8) (the top one <= 8).
+   FD_LAT_SKEW_NW windows are stored; a pair that needs more fails (the caller takes the full-length walk). */
+
+#define FD_LAT_SKEW_T   188
+#define FD_LAT_SKEW_W   17
+#define FD_LAT_SKEW_NW  20
+
+FD_LAT_FN int fd_lat_skew_windows( int bits0, int bits1 ) {
+  int w0 = ( ( bits0 + 4 ) >> 2 ) - 2*FD_LAT_SKEW_W, w1 = ( bits1 + 4 ) >> 2;
+  return w0 > w1 ? w0 : w1;
+}
+
+/* P + Q (8 words; *ovf set on a carry out) and P + Q mod 2^160 (two's complement) */
+FD_LAT_FN void fd_lat_sum8( uint32_t out[ 8 ], uint32_t const P[ 8 ], uint32_t const Q[ 8 ], int * ovf ) {
+  uint64_t c = 0;
+#pragma unroll
+  for( int i=0; i<8; i++ ) { uint64_t v = (uint64_t)P[i] + (uint64_t)Q[i] + c; out[i] = (uint32_t)v; c = v >> 32; }
+  *ovf |= c != 0UL;
+}
+FD_LAT_FN void fd_lat_sum5( uint32_t out[ 5 ], uint32_t const P[ 5 ], uint32_t const Q[ 5 ] ) {
+  uint64_t c = 0;
+#pragma unroll
+  for( int i=0; i<5; i++ ) { uint64_t v = (uint64_t)P[i] + (uint64_t)Q[i] + c; out[i] = (uint32_t)v; c = v >> 32; }
+}
+
+/* k (8 LE words, k < l) -> c0 >= 0 (7 words), |c1| (5 words, odd), sign of c1, with c0 == c1 k (mod 8l) by
+   construction, and the windows the pair needs in *nwin (<= FD_LAT_SKEW_NW: c0 < 2^215, |c1| < 2^79).
+   Returns 0 when no candidate keeps the bound. */
+FD_LAT_FN int fd_lat_skew( uint32_t c0[ 7 ], uint32_t c1m[ 5 ], int * c1neg, int * nwin, uint32_t const k[ 8 ] ) {
+  uint32_t R0[ 8 ] = FD_LAT_N8L, R1[ 8 ], T0[ 5 ] = { 0u, 0u, 0u, 0u, 0u }, T1[ 5 ] = { 1u, 0u, 0u, 0u, 0u };
+#pragma unroll
+  for( int i=0; i<8; i++ ) R1[i] = k[i];
+  int ovf = 0;
+#pragma unroll 1
+  for( int it=0; it<FD_LAT_MAXIT; it++ ) {
+    if( fd_lat_bitlen8( R1 ) <= FD_LAT_SKEW_T ) break;     /* remainder under 2^T */
+    int L = fd_lat_bitlen8( R0 );                          /* R0 >= R1 >= 2^T: L >= T + 1 */
+    int sh = L - 64;
+    uint64_t a = fd_lat_bits64( R0, sh ), b = fd_lat_bits64( R1, sh );
+    int stopb = FD_LAT_SKEW_T + 64 - L;                    /* b < 2^stopb: R1 would drop under ~2^T (stopb <= 63) */
+    uint64_t thr = stopb > 33 ? ( 1UL << stopb ) : ( 1UL << 33 );
+    uint32_t m00 = 1u, m01 = 0u, m10 = 0u, m11 = 1u;
+    int steps = 0;
+#pragma unroll 1
+    for( int j=0; j<FD_LAT_MAXIN; j++ ) {
+      if( b < thr ) break;
+      int s = fd_lat_clz64( b ) - fd_lat_clz64( a );
+      if( s >= 31 ) break;
+      uint64_t bs = b << s;
+      if( bs > a ) { s--; bs >>= 1; }
+      uint64_t n00 = (uint64_t)m00 + ( (uint64_t)m10 << s ), n01 = (uint64_t)m01 + ( (uint64_t)m11 << s );
+      if( ( n00 | n01 ) >> 31 ) break;
+      a -= bs; m00 = (uint32_t)n00; m01 = (uint32_t)n01; steps++;
+      if( a < b ) {
+        uint64_t ta = a; a = b; b = ta;
+        uint32_t t0 = m00; m00 = m10; m10 = t0;
+        uint32_t t1 = m01; m01 = m11; m11 = t1;
+      }
+    }
+    if( !steps ) {                                         /* R0 >> R1: R0 -= 2^s R1, s <= 30 */
+      int s = L - fd_lat_bitlen8( R1 ) - 1;
+      s = s < 0 ? 0 : ( s > 30 ? 30 : s );
+      m00 = 1u; m01 = 1u << s; m10 = 0u; m11 = 1u;
+    }
+    uint32_t nR0[ 8 ], nR1[ 8 ], nT0[ 5 ], nT1[ 5 ];
+    int n0 = fd_lat_comb8( nR0, m00, R0, m01, R1, &ovf );
+    int n1 = fd_lat_comb8( nR1, m11, R1, m10, R0, &ovf );
+    fd_lat_combT( nT0, m00, T0, m01, T1, n0 );
+    fd_lat_combT( nT1, m11, T1, m10, T0, n1 );
+    int sw = fd_lat_lt8( nR0, nR1 );
+#pragma unroll
+    for( int i=0; i<8; i++ ) { R0[i] = sw ? nR1[i] : nR0[i]; R1[i] = sw ? nR0[i] : nR1[i]; }
+#pragma unroll
+    for( int i=0; i<5; i++ ) { T0[i] = sw ? nT1[i] : nT0[i]; T1[i] = sw ? nT0[i] : nT1[i]; }
+  }
+  if( ovf | ( fd_lat_bitlen8( R1 ) > FD_LAT_SKEW_T ) ) return 0;
+
+  /* the candidates with an odd cofactor among (R1, T1), (R0, T0), (R0 - R1, T0 - T1), (R0 + R1, T0 + T1)
+     (the cofactor column has gcd 1, so one of the first two is odd): the one needing the fewest windows */
+  uint32_t cr[ 8 ] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }, ct[ 5 ] = { 0u, 0u, 0u, 0u, 0u };
+  int best = 1 << 20;
+#pragma unroll 1
+  for( int c=0; c<4; c++ ) {
+    uint32_t dr[ 8 ], dt[ 5 ], da[ 5 ];
+    int o2 = 0;
+    if( c < 3 ) {
+      uint32_t x = c != 0, y = c != 1;
+      int ng = fd_lat_comb8( dr, x, R0, y, R1, &o2 );
+      fd_lat_combT( dt, x, T0, y, T1, ng );
+    } else {
+      fd_lat_sum8( dr, R0, R1, &o2 );
+      fd_lat_sum5( dt, T0, T1 );
+    }
+    fd_lat_abs5( da, dt );
+    uint32_t da8[ 8 ] = { da[0], da[1], da[2], da[3], da[4], 0u, 0u, 0u };
+    int nw = fd_lat_skew_windows( fd_lat_bitlen8( dr ), fd_lat_bitlen8( da8 ) );
+    if( ( da[0] & 1u ) && !o2 && nw < best ) {
+      best = nw;
+#pragma unroll
+      for( int i=0; i<8; i++ ) cr[i] = dr[i];
+#pragma unroll
+      for( int i=0; i<5; i++ ) ct[i] = dt[i];
+    }
+  }
+  if( best > FD_LAT_SKEW_NW ) return 0;
+  *c1neg = fd_lat_abs5( c1m, ct );
+#pragma unroll
+  for( int i=0; i<7; i++ ) c0[i] = cr[i];
+  *nwin = best;
+  /* (best <= FD_LAT_SKEW_NW: c0 < 2^(4 (2W + NW) - 1) = 2^215, so cr[7] = 0, and |c1| < 2^79) */
+  return (int)( c1m[0] & 1u ) & ( cr[7] == 0u );
+}

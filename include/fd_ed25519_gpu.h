@@ -392,6 +392,15 @@ fdgpu_ed25519_slow_count( fdgpu_ed25519_ctx_t * ctx );
 unsigned long
 fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx );
 
+/* Repeated keys of the last batch launched on ctx: the public keys with at
+   least FD_HOT_MIN (8) signatures in it, and the signatures of those keys,
+   which walk 64 doublings instead of 128 (either pointer may be NULL).
+   Both 0 when that batch took another path, was not de-duplicated in
+   full, or the split is off (fdgpu_debug_opts_t.key_split).  Waits for
+   the batch; 0 on success. */
+int
+fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, unsigned long * hot_sigs );
+
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
                     unsigned long *       out_tags,
@@ -737,6 +746,10 @@ typedef struct fdgpu_debug_opts {
                                         decoded once (fd_keydedup_kernel); 1 = off, every signature decodes its own
                                         key (A/B: exactly the kernels without it); 2 = TESTS, on with a 64-slot table
                                         and two probes, so most keys fall back to being their own representative */
+  int           key_split;           /* half-size throughput path with key_dedup on: 0 = default, the signatures of a
+                                        key with at least 8 signatures in the batch walk 64 doublings (fd_keysplit_kernel);
+                                        1 = off (A/B: exactly the kernels and launches without it); 2 = TESTS, a key is
+                                        repeated from 2 signatures on */
 } fdgpu_debug_opts_t;
 
 void
