@@ -1,33 +1,46 @@
 /* fd_ed25519_gpu.hip -- MI355X (gfx950) batch ed25519 verify engine.
 
-   Kernels (one signature per lane, wave64, 256-thread workgroups):
+   256-thread workgroups, wave64.  Every batch (launch_batch) starts with
+   fd_expand_kernel (txn -> signature map; raw-payload batches get it from
+   fd_parse_kernel with the fd_txn_t image and the descriptor) and ends
+   with fd_reduce_kernel (per transaction, the code of
+   fd_ed25519_verify_batch_single_msg from its signatures' codes).  Between
+   them one of three paths, by the batch's signature count, kernels in
+   launch order:
 
-     fd_expand_kernel  txn -> signature map (sig_base prefix from the stager)
-     fd_prep_kernel    per signature: S < l, decode A and R (two
-                       interleaved pow22523 chains), small-order tests,
-                       SHA-512(R||A||M) straight from the payload, k mod l,
-                       signed radix-16 digits of k / radix-256 digits of S,
-                       the 9-entry table [0..8](-A) (cached form) -> HBM
-     fd_dsm_kernel     [k](-A) + [S]B by signed fixed windows: 252
-                       doublings, 64 table adds (entries gathered from HBM,
-                       prefetched one window ahead), 16 base-point adds from
-                       the [0..32768]B affine table (L2 / Infinity Cache
-                       resident); projective compare with R ->
-                       FD_ED25519_SUCCESS / ERR_MSG
-     fd_reduce_kernel  per transaction: fd_ed25519_verify_batch_single_msg
-                       code from its signatures' codes
-     large batches (the half-size throughput path) split
-     the prep: fd_keydedup_kernel (a representative signature per distinct
-     public key of the batch), fd_decode_kernel (roles by block: A and its
-     table for the representatives, R and its table for every signature),
-     fd_hashh_kernel (codes, SHA-512, the half-size scalars), then the walk
-     fd_dsmh_kernel (-A entries gathered at the representative's index);
-     fd_keysplit_kernel orders the signatures of keys the batch
-     repeats ahead of the others, and those walk 64 doublings instead of 128
-     over the key's high tables [2^68](-A), [2^136](-A)
-     fd_parse_kernel   (raw-payload batches) per transaction: fd_txn_parse,
-                       fd_txn_t image, and the descriptor the kernels
-                       above consume
+   Latency path (launch_latency; at most FD_SMALL_BATCH_MAX signatures,
+   which cannot fill the GPU).  fd_prep_kernel: roles by block, side by
+   side -- decode A and its table [1..8](-A), decode R and [1..8](-R), and
+   S < l, SHA-512(R||A||M), k mod l and the half-size pair (c0, c1) with
+   s' = c1 S (fd_gpu_lattice.h), the hash on a quad of lanes for the
+   smallest batches.  Then the walk [s']B + [c0](-A) + [c1](-R) == O over
+   128 doublings on 8, 4, 2 or 1 lanes per signature as the batch grows:
+   fd_dsm8_kernel, fd_dsm4_kernel, fd_dsm2_kernel, or fd_dsmh_kernel with
+   fd_dsm_slowl_kernel; each runs the result-code procedure and, for the
+   few signatures without a short pair, the full-length walk.  Without
+   half-size scalars (half = 0): fd_prep_kernel, fd_table_kernel ahead of
+   the one-lane walk, and [k](-A) + [S]B over 252 doublings compared with
+   the decoded R in fd_dsm4_kernel, fd_dsm2_kernel or fd_dsm_kernel.
+
+   Half-size throughput path (launch_half).
+   fd_keydedup_kernel: a representative signature per distinct public key.
+   fd_keysplit_kernel: the signatures of keys the batch repeats ordered
+   ahead of the others.  fd_decode_kernel: roles by block, A and its table
+   for the representatives, R and its table for every signature.
+   fd_hashh_kernel: result codes, SHA-512, (c0, c1, s') as signed digits,
+   and the repeated keys' high tables [2^68](-A), [2^136](-A).
+   fd_dsmh_kernel: the walk, -A entries gathered at the representative's
+   index, 128 doublings, or 64 over the high tables for a repeated key's
+   signatures; base-point adds from the [0..32768]([2^e]B) affine tables
+   (L2 / Infinity Cache resident).  fd_dsm_slow_kernel: what the walk's
+   first blocks left of the signatures without a short pair.
+
+   Full-length throughput path (launch_full; half = 0).  fd_decode_kernel
+   (A only), fd_hash_kernel (signed radix-16 digits of k, radix-2^16 of
+   S), fd_table_kernel, fd_dsm_kernel (252 doublings, 64 table adds
+   prefetched one window ahead, 16 base-point adds), then R is compared
+   without decoding it: fd_rprod_kernel, fd_rinv_kernel, fd_rcheck_kernel,
+   fd_rslow_kernel.
 
    Replaces (behaviour, not code) fd_ed25519_verify /
    fd_ed25519_verify_batch_single_msg (src/ballet/ed25519/
@@ -62,53 +75,33 @@
 #define FD_WG 256
 #define FD_ATAB_ENTRIES 9          /* [0..8](-A), cached form, 128 B each */
 #define FD_ATAB_STORED  8          /* [1..8] stored per signature; [0] (the identity) is one shared constant line */
-/* Base-point window: FD_BWIN = 8 keeps [0..128]B (12.4 KB) in LDS and adds
-   it every 2nd A window (32 adds); FD_BWIN = 16 keeps [0..32768]B (3.1 MB,
-   L2 / Infinity-Cache resident) in HBM, gathered per lane one window
-   ahead, and adds it every 4th A window (16 adds). */
-#ifndef FD_BWIN
+/* Base-point window, fixed at 16 bits: [0..32768]B, affine precomp, 96 B
+   each (3.1 MB, L2 / Infinity-Cache resident) in HBM, gathered per lane
+   one window ahead and added every 4th A window (16 adds).  Every walk and
+   the [2^72]B, [2^120]B, [2^140]B, [2^196]B tables assume this width. */
 #define FD_BWIN 16
-#endif
-#if FD_BWIN==8
-#define FD_BTAB_ENTRIES 129        /* [0..128]B, affine precomp, 96 B each */
-#elif FD_BWIN==16
-#define FD_BTAB_ENTRIES 32769      /* [0..32768]B */
-#else
-#error "FD_BWIN must be 8 or 16"
-#endif
+#define FD_BTAB_ENTRIES 32769
 #define FD_BDIG ( 256 / FD_BWIN )  /* signed radix-2^FD_BWIN digits of S */
 #define FD_ARENA_SLACK  512UL      /* readable bytes past the last payload */
-#ifndef FD_DSM_PREFETCH
-#define FD_DSM_PREFETCH 1          /* issue the -A table gather before the window's doublings */
-#endif
-/* R is not decompressed up front (see the R-check kernels after
-   fd_dsm_kernel); 0 = decode A and R before the DSM and compare
-   projectively at its end. */
-#ifndef FD_DEFER_R
-#define FD_DEFER_R 1
-#endif
+
+/* Path thresholds, in signatures per batch (defaults of the runtime overrides in fdgpu_debug_opts_t). */
+/* Throughput path with half-size scalars (fd_gpu_lattice.h): 128 doublings
+   instead of 252; 0 = the full-length walk with the deferred R check */
+#define FD_HALF 1
 /* Batches of at most this many signatures take the latency path
    (fd_prep_kernel, R decoded up front): they cannot fill the GPU, so
    per-wave instruction streams, not total work, set their time. */
-#ifndef FD_SMALL_BATCH_MAX
 #define FD_SMALL_BATCH_MAX 65536UL
-#endif
 /* fd_dsm_kernel without the carry fold (fd_gpu_f25519.h) for batches of at
    most this many signatures: <= 2 waves per SIMD, where the per-wave chain
    latency, not the instruction count, sets the time */
-#ifndef FD_NOFOLD_MAX
 #define FD_NOFOLD_MAX 131072UL
-#endif
-#ifndef FD_DSM4_MAX
-#define FD_DSM4_MAX 16384UL          /* latency path: four lanes per signature up to here, */
-#endif
-#ifndef FD_DSM2_MAX
+#define FD_DSM8_MAX 8192UL           /* latency path: eight lanes per signature up to here, */
+#define FD_DSM4_MAX 16384UL          /* four up to here, */
 #define FD_DSM2_MAX 32768UL          /* then two up to here, then one (fd_dsm_kernel, R compared at its end) */
-#endif
-#ifndef FD_QSHA_MAX
 #define FD_QSHA_MAX 8192UL           /* latency path: the prep's hash role on a quad of lanes per signature up to here
                                         (fd_sha512_RAM_quad; 6 sg workgroups stay under one wave per SIMD) */
-#endif
+
 #define FD_STAGE_CHUNK ( 1UL << 20 )   /* host-staged batches: bytes per memcpy / H2D step */
 /* gathered batches: the fd_txn_t image of the last record may end this far past its record */
 #define FD_IMG_TAIL    1024UL
@@ -117,22 +110,7 @@
 #define FD_PEND_ASMALL 2           /* per-signature code in flight: A small order, R's decode picks ERR_SIG / ERR_PUBKEY */
 #define FD_PEND_REQ    3           /* per-signature code in flight: P's encoding != R's bytes -> decode R, compare */
 #define FD_PEND_SLOW   4           /* per-signature code in flight: no half-size scalars, full 253-bit walk (fd_dsm_slow_kernel) */
-/* Throughput path with half-size scalars (fd_gpu_lattice.h): 128 doublings
-   instead of 252; 0 = the full-length walk with the deferred R check (A/B) */
-#ifndef FD_HALF
-#define FD_HALF 1
-#endif
 #define FD_HDIG 40                 /* signed radix-16 digits of c0, c1 (< 2^159); the walk stops at the wave's top one */
-/* carry-fold mode (fd_gpu_f25519.h) of the throughput path's decode and table kernels (A/B knobs) */
-#ifndef FD_DECODE_FM
-#define FD_DECODE_FM FD_CARRY_FOLD
-#endif
-#ifndef FD_TABLE_FM
-#define FD_TABLE_FM FD_CARRY_FOLD
-#endif
-#ifndef FD_HALF_FUSED_TABLE
-#define FD_HALF_FUSED_TABLE 1      /* half-size throughput path: tables built by the decode lanes (0: fd_tableh_kernel) */
-#endif
 #define FD_PSTAT_SLOW 0x80u        /* A-status bit: the signature is on the half-size path's slow list */
 /* fd_keydedup_kernel: workgroups (of sg) whose lanes still look their keys up when the batch before had
    mostly distinct keys -- the sample that decides for the batch after */
@@ -232,10 +210,6 @@ fd_expand_kernel( fdgpu_txn_desc_t const * __restrict__ desc, u32 txn_cnt, u32 *
   }
 }
 
-/* FD_ATAB_MADD: the table's additions of -A in affine form (A/B knob; 0: the cached-form addition) */
-#ifndef FD_ATAB_MADD
-#define FD_ATAB_MADD 1
-#endif
 /* [0..8](-A) in cached form from A's canonical affine coordinates */
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void atab_build( uint4 * __restrict__ tab, u32 s, uint4 const * __restrict__ Axy ) {
@@ -249,19 +223,13 @@ FD_DEV void atab_build( uint4 * __restrict__ tab, u32 s, uint4 const * __restric
   ge_cached c1, c;
   ge_p3_to_cached<FM>( c1, A );
   atab_store( tab, s, 1, c1 );
-#if FD_ATAB_MADD
   /* -A has Z = 1: each step adds it in affine form (ge_add_precomp: 3 multiplications instead of 4) */
   ge_precomp a1; a1.ypx = c1.YpX; a1.ymx = c1.YmX; a1.xy2d = c1.T2d;
-#endif
   ge_p3 cur = A;
 #pragma unroll 1
   for( int e=2; e<FD_ATAB_ENTRIES; e++ ) {
     ge_p1p1 tt;
-#if FD_ATAB_MADD
     ge_add_precomp<FM>( tt, cur, a1 );
-#else
-    ge_add_cached<FM>( tt, cur, c1 );
-#endif
     ge_p1p1_to_p3<FM>( cur, tt );
     ge_p3_to_cached<FM>( c, cur );
     atab_store( tab, s, e, c );
@@ -305,16 +273,9 @@ FD_DEV void decode_one( unsigned char const * __restrict__ payload, fdgpu_txn_de
 }
 
 /* Large batches (deferred R): one lane per signature, A only.  With
-   both = 1 (FD_DEFER_R=0 builds): lane 2s decodes A, lane 2s+1 R. */
-/* FD_DECODE_MINW: minimum waves per SIMD asked of the compiler (A/B; 0 = none: 127 VGPRs, 4 waves) */
-#ifndef FD_DECODE_MINW
-#define FD_DECODE_MINW 0
-#endif
-#if FD_DECODE_MINW
-__global__ void __launch_bounds__( FD_WG, FD_DECODE_MINW )
-#else
+   both = 1: lane 2s decodes A, lane 2s+1 R.  (No minimum waves per SIMD
+   asked of the compiler: 127 VGPRs, 4 waves.) */
 __global__ void __launch_bounds__( FD_WG )
-#endif
 fd_decode_kernel( unsigned char const *    __restrict__ payload,
                   fdgpu_txn_desc_t const * __restrict__ desc,
                   u32 const *              __restrict__ map,
@@ -359,11 +320,11 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
     s = both ? p >> 1 : p; is_r = both ? p & 1u : 0u;
     st = pstat + 2u*s + is_r;
   }
-  decode_one<FD_DECODE_FM>( payload, desc, map, s, is_r, st, Rxy, Axy );
+  decode_one( payload, desc, map, s, is_r, st, Rxy, Axy );
   /* tabA != NULL (half-size path): each lane goes on to its point's table
      when the point decoded, its table writes overlapping the other waves'
      decodes (a separate table kernel is write-heavy: 2.3 KB per signature) */
-  if( tabA && ( *st & 3u )==0u ) atab_build<FD_TABLE_FM>( is_r ? tabR : tabA, s, is_r ? Rxy : Axy );
+  if( tabA && ( *st & 3u )==0u ) atab_build( is_r ? tabR : tabA, s, is_r ? Rxy : Axy );
 }
 
 /* Signed digits of k (radix 16, digA[64][n]) and S (radix 2^FD_BWIN,
@@ -416,9 +377,6 @@ FD_DEV int hs_prepare( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 c0[ HOT ? 7 : 5 
   int ng = 0, nwin = 0;
   if( HOT ) { if( !fd_lat_skew( c0, c1m, &ng, &nwin, k ) ) return 0; }
   else if( !fd_lat_halfsize( c0, c1m, &ng, k ) ) return 0;
-#if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 4     /* timing only (wrong codes): ... up to the lattice reduction */
-  return 0;
-#endif
   c1neg = ng;
   u32 c1lo = ng ? 0u - c1m[0] : c1m[0];
   if( ( c0[0] - c1lo * k[0] ) & 7u ) return 0;                       /* mod 8 */
@@ -625,15 +583,7 @@ FD_DEV void hash_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc
   store_digits( k, Sw, s, n, digA, digB );
 }
 
-/* FD_HASH_MINW: minimum waves per SIMD asked of the compiler for fd_hash_kernel (A/B; 0 = none) */
-#ifndef FD_HASH_MINW
-#define FD_HASH_MINW 0
-#endif
-#if FD_HASH_MINW
-__global__ void __launch_bounds__( FD_WG, FD_HASH_MINW )
-#else
 __global__ void __launch_bounds__( FD_WG )
-#endif
 fd_hash_kernel( unsigned char const *    __restrict__ payload,
                 fdgpu_txn_desc_t const * __restrict__ desc,
                 u32 const *              __restrict__ map,
@@ -648,7 +598,7 @@ fd_hash_kernel( unsigned char const *    __restrict__ payload,
                 uint4 const *            __restrict__ khash ) {
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
-  if( !defer ) {                                 /* FD_DEFER_R=0 builds: both points decoded already */
+  if( !defer ) {                                 /* both points decoded already */
     hash_one( payload, desc, map, s, nsig, semantics, 0, pstat, code_out, digA, digB, Rraw, khash );
     int c = code_out[s];
     if( c==FD_ED25519_SUCCESS || c==FD_ED25519_ERR_SIG )
@@ -698,20 +648,8 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
 #pragma unroll
     for( int i=0; i<4; i++ ) { uint4 v = khash[4*(size_t)s + i]; h[4*i] = v.x; h[4*i+1] = v.y; h[4*i+2] = v.z; h[4*i+3] = v.w; }
   } else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
-#if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 2     /* timing only (wrong codes): the hash role up to SHA-512 */
-  code_out[s] = (i8)( h[0] & 1u ); return;
-#endif
   sc_reduce( k, h );
-#if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 3     /* timing only (wrong codes): ... up to k mod l */
-  code_out[s] = (i8)( k[0] & 1u ); return;
-#endif
   u32 c0[5], c1m[5], sp[8]; int c1neg = 0;
-#if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 4
-  { int ok = hs_prepare( k, Sw, c0, c1m, c1neg, sp ); code_out[s] = (i8)( ok + ( c0[0] & 1u ) ); return; }
-#endif
-#if defined(FD_PREP_PROBE) && FD_PREP_PROBE == 5     /* timing only (wrong codes): ... up to s' (no digits) */
-  { int ok = hs_prepare( k, Sw, c0, c1m, c1neg, sp ); code_out[s] = (i8)( ok + ( sp[0] & 1u ) + ( c0[0] & 1u ) ); return; }
-#endif
   if( KS && hot ) {
     u32 c0h[7];
     if( !( force_slow && s % force_slow == 0u ) && hs_prepare<1>( k, Sw, c0h, c1m, c1neg, sp ) ) {
@@ -770,10 +708,6 @@ FD_DEV void hashh_one_q( unsigned char const * __restrict__ payload, fdgpu_txn_d
   }
 }
 
-/* FD_HASHH_MINW: as FD_DECODE_MINW for fd_hashh_kernel (0: 159 VGPRs, 3 waves) */
-#ifndef FD_HASHH_MINW
-#define FD_HASHH_MINW 0
-#endif
 /* Hot / cold order (fd_keysplit_kernel): the hot signatures fill order[] from the front, the cold ones from the
    back, and the hash and walk kernels run one lane per place in it, in ceil(nh/256) hot blocks followed by the cold
    blocks (at most sg + 1 in all), so a wave -- a whole block -- is all hot or all cold.  b: the block's index among
@@ -820,12 +754,9 @@ FD_DEV void htab_build( uint4 * __restrict__ htab, u32 hi, u32 part, uint4 const
   }
 }
 
+/* (no minimum waves per SIMD asked of the compiler: the lattice reduction sets 159 VGPRs, 3 waves) */
 template<int KS>
-#if FD_HASHH_MINW
-__global__ void __launch_bounds__( FD_WG, FD_HASHH_MINW )
-#else
 __global__ void __launch_bounds__( FD_WG )
-#endif
 fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  fdgpu_txn_desc_t const * __restrict__ desc,
                  u32 const *              __restrict__ map,
@@ -858,7 +789,7 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
       if( ( i >> 1 ) >= kscnt[0] ) return;
       u32 rep = hlist[ i >> 1 ];
       if( astat[rep] & 7u ) return;
-      htab_build<FD_TABLE_FM>( htab, i >> 1, i & 1u, Axy, rep );
+      htab_build( htab, i >> 1, i & 1u, Axy, rep );
       return;
     }
     u32 col; int hot;
@@ -871,37 +802,6 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
   if( s >= nsig ) return;
   hashh_one( payload, desc, map, s, nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt, khash,
              force_slow, htop, arep, astat );
-}
-
-/* FD_SHA_SPLIT (A/B): the half-size throughput path hashes in a kernel of its own, at the occupancy the
-   SHA-512 registers allow, instead of inside fd_hashh_kernel, whose lattice reduction sets 159 VGPRs (3
-   waves per SIMD) for the whole hash; fd_hashh_kernel then reads the digests (its khash input) */
-#ifndef FD_SHA_SPLIT
-#define FD_SHA_SPLIT 0
-#endif
-#ifndef FD_SHA_MINW
-#define FD_SHA_MINW 4
-#endif
-__global__ void __launch_bounds__( FD_WG, FD_SHA_MINW )
-fd_sha_kernel( unsigned char const *    __restrict__ payload,
-               fdgpu_txn_desc_t const * __restrict__ desc,
-               u32 const *              __restrict__ map,
-               u32                                   nsig,
-               uint4 *                  __restrict__ dig ) {
-  u32 s = blockIdx.x * FD_WG + threadIdx.x;
-  if( s >= nsig ) return;
-  u32 m = map[s];
-  u32 t = m & 0xffffffu, j = m >> 24;
-  fdgpu_txn_desc_t d = desc[t];
-  if( !txn_desc_ok( d ) ) return;
-  unsigned char const * base = payload + d.payload_off;
-  u32 Rw[8], Aw[8], h[16];
-  fd_load_words<8>( Rw, base + d.signature_off + 64u*j );
-  fd_load_words<8>( Aw, base + d.acct_addr_off + 32u*j );
-  fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
-  uint4 * o = dig + 4*(size_t)s;
-#pragma unroll
-  for( int i=0; i<4; i++ ) o[i] = make_uint4( h[4*i], h[4*i+1], h[4*i+2], h[4*i+3] );
 }
 
 /* Small batches (latency): the three independent parts of the prep in
@@ -929,17 +829,6 @@ FD_DEV void prep_role( unsigned char const * __restrict__ payload, fdgpu_txn_des
                            khash, force_slow, htop );
   else hash_one( payload, desc, map, s, nsig, semantics, 0, pstat, code_out, digA, digB, Rxy, khash );
 }
-
-/* FD_PREP_PROBE builds (tools/prep_probe.py, A/B only): lane 0 of every wave of fd_prep_kernel records
-   its start and end on the 100 MHz real-time counter and its role, so the length of each role's
-   chain in a latency-path batch is measured (fdgpu_debug_prep_probe) */
-#ifndef FD_PREP_PROBE
-#define FD_PREP_PROBE 0
-#endif
-#if FD_PREP_PROBE
-#define FD_PP_WAVES 4096
-__device__ unsigned long long fd_pp_buf[ FD_PP_WAVES ][ 3 ];
-#endif
 
 /* QS = 1 (half-size walk, batches of at most FD_QSHA_MAX signatures): the hash role on a quad of lanes per
    signature (hashh_one_q), blocks [2 sg, 6 sg) */
@@ -973,22 +862,6 @@ fd_prep_kernel( unsigned char const *    __restrict__ payload,
     role = blockIdx.x / sg;
     s = ( blockIdx.x - role*sg ) * FD_WG + threadIdx.x;
   }
-#if FD_PREP_PROBE
-  unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  if( s < nsig ) {
-    if( QS && role == 2u )
-      hashh_one_q( payload, desc, map, s, nsig, code_out, digA, digR, digB, slow, slow_cnt, khash, force_slow, htop,
-                   threadIdx.x & 3u, threadIdx.x & 60u );
-    else
-      prep_role<FM,HS>( payload, desc, map, nsig, role, s, semantics, pstat, Rxy, Axy, code_out, digA, digB,
-                        tab, khash, tabR, digR, slow, slow_cnt, force_slow, htop );
-  }
-  unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-  u32 wv = blockIdx.x * ( FD_WG / 64u ) + threadIdx.x / 64u;
-  if( ( threadIdx.x & 63u ) == 0u && wv < FD_PP_WAVES && s < nsig ) {
-    fd_pp_buf[ wv ][0] = t0; fd_pp_buf[ wv ][1] = t1; fd_pp_buf[ wv ][2] = role;
-  }
-#else
   if( s >= nsig ) return;                        /* (a quad's four lanes leave together) */
   if( QS && role == 2u ) {
     hashh_one_q( payload, desc, map, s, nsig, code_out, digA, digR, digB, slow, slow_cnt, khash, force_slow, htop,
@@ -997,24 +870,7 @@ fd_prep_kernel( unsigned char const *    __restrict__ payload,
   }
   prep_role<FM,HS>( payload, desc, map, nsig, role, s, semantics, pstat, Rxy, Axy, code_out, digA, digB,
                     tab, khash, tabR, digR, slow, slow_cnt, force_slow, htop );
-#endif
 }
-
-#if FD_PREP_PROBE
-/* the probe records of the last fd_prep_kernel launch (its waves in launch order): n of [start, end, role] */
-extern "C" int
-fdgpu_debug_prep_probe( unsigned long long * out, unsigned long n ) {
-  if( n > FD_PP_WAVES ) n = FD_PP_WAVES;
-  if( hipDeviceSynchronize() != hipSuccess ) return -1;
-  return hipMemcpyFromSymbol( out, HIP_SYMBOL( fd_pp_buf ), n * 3 * sizeof(unsigned long long), 0, hipMemcpyDeviceToHost )
-         == hipSuccess ? 0 : -1;
-}
-extern "C" int
-fdgpu_debug_prep_probe_clear( void ) {
-  static unsigned long long z[ FD_PP_WAVES ][ 3 ];
-  return hipMemcpyToSymbol( HIP_SYMBOL( fd_pp_buf ), z, sizeof(z), 0, hipMemcpyHostToDevice ) == hipSuccess ? 0 : -1;
-}
-#endif
 
 /* Stage 3 -- table [0..8](-A) in cached form (fd_ed25519_point_neg + the
    odd-multiple table of fd_curve25519.c:118-131; here all multiples, for a
@@ -1032,32 +888,6 @@ fd_table_kernel( u32 nsig, int semantics, unsigned char const * __restrict__ pst
   atab_build( tab, s, Axy );
 }
 
-/* FD_CLOCK_PROBE builds (tools/clock_probe.py): lane 0 of every
-   fd_dsm_kernel block records the shader clock counter (s_memtime) and the
-   100 MHz real-time counter (s_memrealtime) at its start and end, so the
-   clock the kernel actually ran at is measured, not assumed. */
-#ifndef FD_CLOCK_PROBE
-#define FD_CLOCK_PROBE 0
-#endif
-#if FD_CLOCK_PROBE
-#define FD_CLK_BLOCKS 16384
-__device__ unsigned long long fd_clk_buf[ FD_CLK_BLOCKS ][ 4 ];
-#define FD_CLK_BEGIN unsigned long long fd_c0 = __builtin_amdgcn_s_memtime(), fd_r0 = __builtin_amdgcn_s_memrealtime();
-#define FD_CLK_END if( threadIdx.x == 0 && blockIdx.x < FD_CLK_BLOCKS ) {                                         \
-    unsigned long long fd_c1 = __builtin_amdgcn_s_memtime(), fd_r1 = __builtin_amdgcn_s_memrealtime();            \
-    fd_clk_buf[ blockIdx.x ][0] = fd_c0; fd_clk_buf[ blockIdx.x ][1] = fd_c1;                                      \
-    fd_clk_buf[ blockIdx.x ][2] = fd_r0; fd_clk_buf[ blockIdx.x ][3] = fd_r1; }
-#else
-#define FD_CLK_BEGIN
-#define FD_CLK_END
-#endif
-
-/* FD_DSM_MINW: minimum waves per SIMD asked of the compiler for
-   fd_dsm_kernel (0: none; the register count then decides, 162 VGPRs ->
-   3 waves) */
-#ifndef FD_DSM_MINW
-#define FD_DSM_MINW 0
-#endif
 /* [k](-A) + [S]B for signature s (full-length signed fixed windows; body of
    fd_dsm_kernel and of fd_dsm_slow_kernel).  defer: store P for the R-check
    kernels; else compare with the decoded R and write the code. */
@@ -1072,22 +902,16 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
   atab_raw raw;
   int da = digA[ (size_t)63*n + col ];
 
-#if FD_BWIN==16
   uint4 braw[6]; int db = 0;
-#endif
 #pragma unroll 1
   for( int w=63; w>=0; w-- ) {
-#if FD_DSM_PREFETCH
-    atab_fetch( raw, tab, sa, da < 0 ? -da : da );   /* in flight during the doublings */
-#endif
-#if FD_BWIN==16
+    atab_fetch( raw, tab, sa, da < 0 ? -da : da );   /* issued before the window's doublings: in flight during them */
     if( !(w & 3) ) {                                 /* base-point entry, also in flight */
       db = digB[ (size_t)(w>>2)*n + col ];
       uint4 const * bp = btab + (size_t)( db < 0 ? -db : db )*6;
 #pragma unroll
       for( int i=0; i<6; i++ ) braw[i] = bp[i];
     }
-#endif
     ge_p1p1 t;
     if( w != 63 ) {
 #pragma unroll 1
@@ -1095,26 +919,9 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
       ge_dbl<FM>( t, P2 ); ge_p1p1_to_p3<FM>( P, t );
     }
     {
-#if !FD_DSM_PREFETCH
-      atab_fetch( raw, tab, sa, da < 0 ? -da : da );
-#endif
       ge_cached q; atab_unpack( q, raw ); ge_cached_cneg( q, da < 0 );
       ge_add_cached<FM>( t, P, q );
     }
-#if FD_BWIN==8
-    if( !(w & 1) ) {
-      ge_p1p1_to_p3<FM>( P, t );
-      int db = digB[ (size_t)(w>>1)*n + col ];
-      int e = db < 0 ? -db : db;
-      uint4 const * bp = btab + e*6;
-      ge_precomp bq;
-      fe_from_quads( bq.ypx,  bp[0], bp[1] );
-      fe_from_quads( bq.ymx,  bp[2], bp[3] );
-      fe_from_quads( bq.xy2d, bp[4], bp[5] );
-      ge_precomp_cneg( bq, db < 0 );
-      ge_add_precomp<FM>( t, P, bq );
-    }
-#else
     if( !(w & 3) ) {
       ge_p1p1_to_p3<FM>( P, t );
       ge_precomp bq;
@@ -1124,7 +931,6 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
       ge_precomp_cneg( bq, db < 0 );
       ge_add_precomp<FM>( t, P, bq );
     }
-#endif
     ge_p1p1_to_p2<FM>( P2, t );
     if( w > 0 ) da = digA[ (size_t)(w-1)*n + col ];
   }
@@ -1147,34 +953,22 @@ FD_DEV void dsm_one( u32 s, size_t n, uint4 const * __restrict__ tab, uint4 cons
   code[s] = (okx & oky) ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
 }
 
+/* (no minimum waves per SIMD asked of the compiler: the register count decides, 162 VGPRs -> 3 waves) */
 template<int FM>
-#if FD_DSM_MINW
-__global__ void __launch_bounds__( FD_WG, FD_DSM_MINW )
-#else
 __global__ void __launch_bounds__( FD_WG )
-#endif
 fd_dsm_kernel( u32                      nsig,
                uint4 const * __restrict__ tab,
                uint4 const * __restrict__ Rxy,
                i8 const *    __restrict__ digA,
                short const * __restrict__ digB,
-               uint4 const * __restrict__ btab_g,
+               uint4 const * __restrict__ btab,
                i8 *          __restrict__ code,
                u32 *         __restrict__ Pbuf,
                int                        defer ) {
-#if FD_BWIN==8
-  __shared__ uint4 btab[ FD_BTAB_ENTRIES * 6 ];
-  for( int i=threadIdx.x; i<FD_BTAB_ENTRIES*6; i+=FD_WG ) btab[i] = btab_g[i];
-  __syncthreads();
-#else
-  uint4 const * btab = btab_g;
-#endif
-  FD_CLK_BEGIN
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   if( s >= nsig ) return;
   if( code[s] != FD_ED25519_SUCCESS ) return;
   dsm_one<FM>( s, nsig, tab, Rxy, digA, digB, btab, code, Pbuf, defer, s, s );
-  FD_CLK_END
 }
 
 /* Half-size path: the signatures on the slow list (no short (c0, c1)) take
@@ -1224,20 +1018,6 @@ fd_dsm_slowl_kernel( u32 nsig, uint4 const * __restrict__ tab, uint4 const * __r
   slowl_tail<FM>( nsig, tab, Rxy, digA, digB, btab, code, slow, slow_cnt, semantics, pstat );
 }
 
-/* Half-size path tables: blocks [0,sg) build [0..8](-A) for every pending
-   signature (also the slow ones), blocks [sg,2sg) [0..8](-R) for the
-   half-size ones. */
-__global__ void __launch_bounds__( FD_WG, 3 )
-fd_tableh_kernel( u32 nsig, u32 sg, i8 const * __restrict__ code, uint4 const * __restrict__ Axy,
-                  uint4 const * __restrict__ Rxy, uint4 * __restrict__ tabA, uint4 * __restrict__ tabR ) {
-  u32 role = blockIdx.x >= sg, b = blockIdx.x - role*sg;
-  u32 s = b * FD_WG + threadIdx.x;
-  if( s >= nsig ) return;
-  int c = code[s];
-  if( !role ) { if( c == FD_ED25519_SUCCESS || c == FD_PEND_SLOW ) atab_build<FD_TABLE_FM>( tabA, s, Axy ); }
-  else if( c == FD_ED25519_SUCCESS ) atab_build<FD_TABLE_FM>( tabR, s, Rxy );
-}
-
 /* Half-size DSM: Q = [s']B + [c0](-A) + [c1](-R) by a joint signed
    fixed-window walk over (normally) 33 windows of 4 bits -- 128 doublings,
    33 -A adds and 33 -R adds (both tables gathered from HBM, the -A entry
@@ -1246,15 +1026,7 @@ fd_tableh_kernel( u32 nsig, u32 sg, i8 const * __restrict__ code, uint4 const * 
    [0..32768](2^120 B) (digits 8-15).
    Q == O (X == 0, Y == Z)  <=>  R == [S]B - [k]A  (fd_gpu_lattice.h). */
 /* FD_DSMH_MINW: waves per SIMD asked of the compiler (3: <= 168 VGPRs) */
-#ifndef FD_DSMH_MINW
 #define FD_DSMH_MINW 3
-#endif
-/* FD_DSMH_LDS: dynamic LDS (bytes, <= 64 KiB) reserved per workgroup of the throughput walk, which uses none:
-   a cap on its workgroups per CU below the register limit's 3 (A/B: 57344 -> 2 per CU, so a 1M batch's
-   16 waves per SIMD run in 8 full rounds instead of 5 and a lone wave) */
-#ifndef FD_DSMH_LDS
-#define FD_DSMH_LDS 0
-#endif
 /* The walk of a hot signature (a key the batch repeats): c0 in three parts of W = 17 windows,
      Q = [s']B + [c0_0](-A) + [c0_1]([2^68](-A)) + [c0_2]([2^136](-A)) + [c1](-R),
    over 17 windows (up to FD_KS_NW when a lane's pair needs them) = 64 doublings.  Per window: 4 doublings, the
@@ -1376,7 +1148,6 @@ fd_dsmh_kernel( u32                      nsig,
     code[s] = ok ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
     return;
   }
-  FD_CLK_BEGIN
   ge_p3 P; ge_p3_identity( P );
   ge_p2 P2;
   atab_raw ra, rr;
@@ -1427,7 +1198,6 @@ fd_dsmh_kernel( u32                      nsig,
   /* Q == O: X == 0 and Y == Z (Z != 0: complete formulas) */
   int ok = fe_is_zero( P2.X ) & fe_eq( P2.Y, P2.Z );
   code[s] = ok ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
-  FD_CLK_END
 }
 
 /* ---- latency path: two lanes per signature ------------------------------
@@ -1455,9 +1225,6 @@ fd_dsmh_kernel( u32                      nsig,
    compiler's own lowering of __builtin_amdgcn_update_dpp gave wrong
    results here on gfx950 -- measured: every valid signature rejected --
    while these moves and a ds_swizzle __shfl_xor agree with the oracle.) */
-#ifndef FD_DSM4_FUSED
-#define FD_DSM4_FUSED 1      /* 4-lane DSM: broadcasts fused into VOP2 DPP adds/subs (0: separate moves, for A/B) */
-#endif
 #define FD_DPP_MOV( d, a, PERM ) "v_mov_b32_dpp %" #d ", %" #a " " PERM " row_mask:0xf bank_mask:0xf\n\t"
 /* r = a as seen through one quad_perm (10 moves, one asm block) */
 #define FD_DEF_FE_DPP( name, PERM )                                                        \
@@ -1488,7 +1255,7 @@ FD_DEF_FE_DPP( fe_swap23, "quad_perm:[0,1,3,2]" )       /* lanes 2 and 3 trade *
 FD_DEF_U32_DPP( fd_bcast0, "quad_perm:[0,0,0,0]" )
 FD_DEF_U32_DPP( fd_bcast1, "quad_perm:[1,1,1,1]" )
 
-/* Broadcast fused into the arithmetic: r = OP( quad lane k's a, this lane's b ),
+/* Broadcast fused into the arithmetic (quad_dbl, quad_add): r = OP( quad lane k's a, this lane's b ),
    one VOP2 DPP instruction per limb (the DPP applies to src0).  v_add_u32 is
    a + b, v_subrev_u32 is b - a; limbs wrap mod 2^32 exactly as the unfused
    forms do, so every result is bit-identical to bcast-then-op. */
@@ -1748,7 +1515,6 @@ FD_DEV void quad_mstep( fe & m, int q, fe const & E, fe const & F, fe const & G,
 
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void quad_dbl( fe & E, fe & F, fe & G, fe & H, int q, fe const & m ) {
-#if FD_DSM4_FUSED
   fe y, a, sq, XX, YY, t, t2;
   fe_bcast1( y, m );
   fe_add_q0( t, m, y );                              /* X + Y */
@@ -1759,25 +1525,12 @@ FD_DEV void quad_dbl( fe & E, fe & F, fe & G, fe & H, int q, fe const & m ) {
   fe_sub( G, YY, XX );                               /* G = YY-XX (L) */
   fe_sub_q3( t, sq, H ); fe_addc( E, t, 1 ); fe_wcarry( E, E );   /* E = SS-H+4p = 2XY */
   fe_csub4( t, G ); fe_add_q2( t2, sq, t ); fe_add_q2( F, sq, t2 ); fe_wcarry( F, F );   /* F = 2ZZ-G+4p */
-#else
-  fe x, y, a, sq, XX, YY, ZZ, SS, t;
-  fe_bcast0( x, m ); fe_bcast1( y, m );
-  fe_add( t, x, y );
-  fe_sel( a, q==3, t, m );                           /* X, Y, Z, X+Y */
-  fe_sqr<FM>( sq, a );
-  fe_bcast0( XX, sq ); fe_bcast1( YY, sq ); fe_bcast2( ZZ, sq ); fe_bcast3( SS, sq );
-  fe_add( H, YY, XX );                               /* H = YY+XX (L) */
-  fe_sub( G, YY, XX );                               /* G = YY-XX (L) */
-  fe_sub4( E, SS, H ); fe_wcarry( E, E );            /* E = SS-H = 2XY */
-  fe_add( t, ZZ, ZZ ); fe_sub4( F, t, G ); fe_wcarry( F, F );   /* F = 2ZZ-G */
-#endif
 }
 
 /* P + Q; lane q passes the coordinate of Q it multiplies by (Y2+X2,
    Y2-X2, 2dT2, Z2), already conditionally negated */
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void quad_add( fe & E, fe & F, fe & G, fe & H, int q, fe const & m, fe const & c ) {
-#if FD_DSM4_FUSED
   fe x, w, a, b, u, n, B, C, D, D2, t;
   fe_bcast0( x, m ); fe_swap23( w, m );              /* lane 2: T, lane 3: Z */
   fe_add_q1( a, m, x );                              /* Y+X */
@@ -1791,21 +1544,6 @@ FD_DEV void quad_add( fe & E, fe & F, fe & G, fe & H, int q, fe const & m, fe co
   fe_bcast3( D, n ); fe_add_q3( D2, n, D );          /* D2 = 2 Z Z2 (L) */
   fe_add_q2( G, n, D2 );                             /* G = D2+C */
   fe_bcast2( C, n ); fe_sub4( F, D2, C ); fe_wcarry( F, F );        /* F = D2-C+4p */
-#else
-  fe x, y, w, a, b, u, n, A, B, C, D;
-  fe_bcast0( x, m ); fe_bcast1( y, m ); fe_swap23( w, m );   /* lane 2: T, lane 3: Z */
-  fe_add( a, y, x );
-  fe_sub( b, y, x );
-  fe_sel( u, q==1, b, a );
-  fe_sel( u, q>=2, w, u );
-  fe_mul<FM>( n, u, c );
-  fe_bcast0( A, n ); fe_bcast1( B, n ); fe_bcast2( C, n ); fe_bcast3( D, n );
-  fe_add( D, D, D );                                 /* D = 2 Z Z2 (L) */
-  fe_sub( E, A, B );
-  fe_add( H, A, B );
-  fe_add( G, D, C );
-  fe_sub4( F, D, C ); fe_wcarry( F, F );
-#endif
 }
 
 template<int FM, int HS>
@@ -1941,9 +1679,6 @@ fd_dsm4_kernel( u32                      nsig,
    form (Y+X, Y-X, 2dT, Z; one multiplication), is added to quad 0's, and
    the sum is tested for the identity.  Every lane of a group leaves
    together (result codes first, like fd_dsm4_kernel<.,1>). */
-#ifndef FD_DSM8_MAX
-#define FD_DSM8_MAX 8192UL
-#endif
 FD_DEV void fe_from_upper_quad( fe & r, fe const & a ) {   /* lanes 0-3 of a group of 8 read lanes 4-7 */
   asm volatile( "s_nop 1\n\t"
                 FD_DPP_MOV( 0, 10, "row_shl:4" ) FD_DPP_MOV( 1, 11, "row_shl:4" ) FD_DPP_MOV( 2, 12, "row_shl:4" )
@@ -2066,7 +1801,7 @@ fd_dsm8_kernel( u32                      nsig,
   slowl_tail<FM>( nsig, tabA, Rxy, digA, digB, btab, code, slow, slow_cnt, semantics, pstat );
 }
 
-/* ---- deferred R check (FD_DEFER_R) ---------------------------------------
+/* ---- deferred R check ----------------------------------------------------
    The signature's R is never decompressed on the common path.
    fd_dsm_kernel leaves P = [k](-A) + [S]B projective, and P's affine
    encoding is compared with the 32 bytes of R:
@@ -2832,10 +2567,10 @@ struct fdgpu_ed25519_ctx {
   unsigned      excl_lds[ 8 ];   /* fdgpu_ed25519_set_cu_exclusive: dynamic LDS per workgroup of the latency path's
                                     prep<0,1>, prep<0,0>, dsm8, dsm4<0,1>, dsm4<0,0>, dsm2<0,1>, dsm2<0,0> (0 = none) */
   unsigned long nofold_max;      /* fd_dsm_kernel<0> (no carry fold) for batches of at most this many signatures */
-  u32 *   d_P;                   /* FD_DEFER_R: P = [k](-A)+[S]B, planar [30][max_sig] limbs */
+  u32 *   d_P;                   /* deferred R: P = [k](-A)+[S]B, planar [30][max_sig] limbs */
   u32 *   d_O;                   /*             product of the block's other Z, planar [10][max_sig] */
   u32 *   d_blk;                 /*             per 256-signature block: product of Z, then its inverse */
-  u32 *   d_slow;                /*             signatures needing R's full decode, [max_sig] + count
+  u32 *   d_slow;                /*             signatures needing R's full decode, [max_sig] + the words of slow_word
                                     (half-size path: signatures without a short (c0, c1)) */
   int     half;                  /* throughput path with half-size scalars (env FDGPU_HALF, default FD_HALF) */
   u32     half_force_slow;       /* tests: signatures with s % m == 0 take the full walk (env FDGPU_HALF_FORCE_SLOW) */
@@ -2844,7 +2579,6 @@ struct fdgpu_ed25519_ctx {
   unsigned char * d_htop;        /*                 highest nonzero window of c0 / c1, [max_sig] */
   uint4 * d_btab2;               /*                 [0..32768](2^120 B) */
   uint4 * d_khash;               /* NULL, or (drop-in, long messages) SHA-512(R||A||M) per signature, computed beforehand */
-  uint4 * d_kdig;                /* FD_SHA_SPLIT: fd_sha_kernel's digests, [max_sig][4] */
   int     key_dedup;             /* half-size throughput path: distinct keys decoded once.  The resolved choice, 1 = on,
                                     0 = off -- not the value of fdgpu_debug_opts_t.key_dedup (0 on, 1 off, 2 tests) */
   u32 *   d_ktab;                /*   fd_keydedup_kernel's table, kd_slots 32-bit slots (>= 2 max_sig: load <= 0.5) */
@@ -3028,7 +2762,6 @@ static int async_busy( fdgpu_ed25519_ctx_t const * ctx ) {
   return 0;
 }
 
-/* flags: 1 = the map is written already (fused into fd_parse_kernel), 2 = no reduce (fd_finish_kernel does it) */
 /* the engine path a batch of nsig signatures takes: latency-path lanes per signature in the walk (8, 4, 2,
    1) or FDGPU_PATH_THROUGHPUT(_FULL) -- launch_batch's choice, also known before its launch (slot_launch_) */
 static int pick_path( fdgpu_ed25519_ctx_t const * ctx, unsigned long nsig ) {
@@ -3053,196 +2786,186 @@ static int pick_path( fdgpu_ed25519_ctx_t const * ctx, unsigned long nsig ) {
   return ctx->half ? FDGPU_PATH_THROUGHPUT : FDGPU_PATH_THROUGHPUT_FULL;
 }
 
+/* The words after d_slow[max_sig]: a batch's device-side counts (slow_word) */
+enum {
+  FD_SW_SLOW     = 0,   /* the slow list's count */
+  FD_SW_KEYS     = 1,   /* the distinct keys' count; from here ucnt[0..2] of fd_keydedup_kernel and fd_decode_kernel */
+  FD_SW_DISTINCT = 2,   /* were most keys of the batch before distinct? */
+  FD_SW_SAMPLE   = 3,   /* the count of the sample that decides it */
+  FD_SW_HOT      = 4,   /* the hot keys, then the hot and the cold signatures: fd_keysplit_kernel's three counters */
+  FD_SW_CNT      = 8 };
+static u32 * slow_word( fdgpu_ed25519_ctx_t const * ctx, int w ) { return ctx->d_slow + ctx->max_sig + w; }
+
+/* What every kernel launch of one batch shares */
+struct fd_batch {
+  unsigned char const *    d_payload;
+  fdgpu_txn_desc_t const * d_desc;
+  u32                      nsig;
+  unsigned                 sg;     /* workgroups of one lane per signature */
+  i8 *                     code;   /* the per-signature codes */
+  hipStream_t              st;
+  hipEvent_t *             ev;     /* recorded while ctx->timing: [0] prep start, [1] walk start, [2] walk end,
+                                      [3] reduce end, [4] (half-size throughput path) the decode kernel's end */
+};
+
+/* Latency path: a batch that cannot fill the GPU, so its time is the sum of the kernels' per-wave instruction
+   streams -- decode A, decode R and hash side by side in one launch (fd_prep_kernel), then the walk on `lanes`
+   lanes per signature with R compared at its end (no R-check chain and its inversion). */
+static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int lanes ) {
+  u32 nsig = b.nsig; unsigned sg = b.sg; i8 * code = b.code; hipStream_t st = b.st;
+  int hs = ctx->half;                                           /* half-size scalars */
+  int qs = hs && ctx->quad_sha >= 0 && nsig <= FD_QSHA_MAX;     /* the hash role on quads (fd_sha512_RAM_quad) */
+  int d2 = lanes > 1;
+  u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW );
+  /* half-size: the A and R lanes build both tables, the hash lane (c0, c1, s'); else the A lane builds -A's
+     table for the 4- and 2-lane walks, and fd_table_kernel builds it for the one-lane walk */
+  hipLaunchKernelGGL( ( qs ? fd_prep_kernel<0,1,1> : hs ? fd_prep_kernel<0,1> : fd_prep_kernel<0,0> ),
+                      dim3( ( qs ? 6 : 3 )*sg ), dim3(FD_WG), ctx->excl_lds[ qs ? 7 : hs ? 0 : 1 ], st, b.d_payload, b.d_desc,
+                      ctx->d_map, nsig, (u32)sg, ctx->semantics, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, code, ctx->d_digA,
+                      ctx->d_digB, hs || d2 ? ctx->d_tab : (uint4 *)NULL, (uint4 const *)ctx->d_khash,
+                      hs ? ctx->d_tabR : (uint4 *)NULL, hs ? ctx->d_digR : (i8 *)NULL, hs ? ctx->d_slow : (u32 *)NULL,
+                      hs ? slow_cnt : (u32 *)NULL, hs ? ctx->half_force_slow : 0u, hs ? ctx->d_htop : (unsigned char *)NULL );
+  if( !hs && !d2 )
+    hipLaunchKernelGGL( fd_table_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, ctx->d_pstat, code,
+                        ctx->d_Axy, ctx->d_tab );
+  if( ctx->timing ) hipEventRecord( b.ev[1], st );
+  if( lanes==8 )
+    hipLaunchKernelGGL( fd_dsm8_kernel<0>, dim3(8*sg), dim3(FD_WG), ctx->excl_lds[2], st, nsig, ctx->d_tab, ctx->d_tabR,
+                        ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->semantics, ctx->d_pstat,
+                        ctx->d_htop, ctx->d_Rxy, ctx->d_slow, slow_cnt );
+  else if( lanes==4 || lanes==2 )
+    hipLaunchKernelGGL( ( lanes==4 ? ( hs ? fd_dsm4_kernel<0,1> : fd_dsm4_kernel<0,0> )
+                                   : ( hs ? fd_dsm2_kernel<0,1> : fd_dsm2_kernel<0,0> ) ),
+                        dim3(lanes*sg), dim3(FD_WG), ctx->excl_lds[ ( lanes==4 ? 3 : 5 ) + !hs ], st, nsig, ctx->d_tab,
+                        ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->semantics, ctx->d_pstat,
+                        ctx->d_tabR, ctx->d_digR, ctx->d_btab2, ctx->d_htop, ctx->d_slow, slow_cnt );
+  else if( hs )                                /* one lane: the half-size walk, result codes at its start */
+    hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
+                        ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, 0u,
+                        ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL, (u32 const *)NULL,
+                        (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL );
+  else                                         /* one lane, full length (no carry fold up to nofold_max) */
+    hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
+                        nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 0 );
+  if( ctx->timing ) hipEventRecord( b.ev[2], st );
+  if( hs && lanes <= 1 )                       /* slow list (normally empty); the 8/4/2-lane walks ran it */
+    hipLaunchKernelGGL( fd_dsm_slowl_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
+                        ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt, ctx->semantics, ctx->d_pstat );
+  return 0;
+}
+
+/* Half-size throughput path: each distinct key decoded once (fd_keydedup_kernel), the signatures of repeated keys
+   ordered ahead of the others (fd_keysplit_kernel), fd_decode_kernel (A and R with their tables), fd_hashh_kernel
+   (result codes, hash, (c0, c1, s'), the hot keys' high tables), then the walk fd_dsmh_kernel with the head of the
+   slow list in its first blocks, and fd_dsm_slow_kernel for the rest. */
+static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
+  u32 nsig = b.nsig; unsigned sg = b.sg; i8 * code = b.code; hipStream_t st = b.st;
+  int kd = ctx->key_dedup, ks = ctx->key_split;                   /* (ks needs kd) */
+  u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW ), * ucnt = slow_word( ctx, FD_SW_KEYS );
+  /* kd: A's status and -A's table are the representative's.  ks: lane i <-> signature order[i], hot blocks then
+     cold blocks (at most sg + 1 of them) */
+  u32 const * arep = kd ? ctx->d_arep : NULL, * order = ks ? ctx->d_order : NULL, * hidx = ks ? ctx->d_hidx : NULL;
+  u32 const * kscnt = ks ? slow_word( ctx, FD_SW_HOT ) : NULL;
+  if( kd ) {
+    /* the table cleared for this batch -- the smallest power of two of slots that is twice its signatures, so a
+       small batch on a large context clears little -- then (ks) the signatures per key counted and the batch
+       partitioned into hot and cold */
+    u32 slots = 64u;
+    if( !ctx->kd_tiny ) while( slots < ctx->kd_slots && slots < 2u*nsig ) slots <<= 1;
+    HIPCHK( hipMemsetAsync( ctx->d_ktab, 0, (size_t)slots * sizeof(u32), st ), -3 );
+    if( ks ) HIPCHK( hipMemsetAsync( ctx->d_kcnt, 0, (size_t)nsig * sizeof(u32), st ), -3 );
+    hipLaunchKernelGGL( ( ks ? fd_keydedup_kernel<1> : fd_keydedup_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, b.d_payload,
+                        b.d_desc, ctx->d_map, nsig, ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep,
+                        ctx->d_ulist, ucnt, ctx->d_pstat, FD_KD_SBLK( sg ), ks ? ctx->d_kcnt : (u32 *)NULL,
+                        ks ? ctx->hot_min : 0u );
+    if( ks )
+      hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
+                          (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
+                          slow_word( ctx, FD_SW_HOT ), ctx->hot_cap );
+  }
+  /* kd: A lanes over the representatives in the first sg blocks, R lanes over every signature; else lanes 2s, 2s+1 */
+  hipLaunchKernelGGL( fd_decode_kernel, dim3( kd ? 2*sg : (unsigned)( ( 2UL*nsig + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
+                      b.d_payload, b.d_desc, ctx->d_map, nsig, 1, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR,
+                      kd ? (u32 const *)ctx->d_ulist : NULL, kd ? ucnt : (u32 *)NULL,
+                      kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u );
+  if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
+  /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
+     keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
+  unsigned hb = ks ? (unsigned)( ( 2UL * ( nsig / ctx->hot_min ) + FD_WG - 1 ) / FD_WG ) : 0u;
+  hipLaunchKernelGGL( ( ks ? fd_hashh_kernel<1> : fd_hashh_kernel<0> ), dim3( ks ? hb + sg + 1 : sg ), dim3(FD_WG), 0, st,
+                      b.d_payload, b.d_desc, ctx->d_map, nsig, ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR,
+                      ctx->d_digB, ctx->d_slow, slow_cnt, (uint4 const *)ctx->d_khash, ctx->half_force_slow, ctx->d_htop,
+                      arep, (unsigned char const *)( kd ? ctx->d_astat : NULL ), order, kscnt,
+                      (u32 const *)( ks ? ctx->d_hlist : NULL ), (uint4 const *)( ks ? ctx->d_Axy : NULL ),
+                      ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb );
+  if( ctx->timing ) hipEventRecord( b.ev[1], st );
+  /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the rest (if any) in
+     fd_dsm_slow_kernel */
+  unsigned nsb = ( sg + 63u ) / 64u;
+  int fold = nsig > ctx->nofold_max;
+  hipLaunchKernelGGL( ( fold ? ( ks ? fd_dsmh_kernel<1,1> : fd_dsmh_kernel<1,0> )
+                             : ( ks ? fd_dsmh_kernel<0,1> : fd_dsmh_kernel<0,0> ) ),
+                      dim3( nsb + sg + ( ks ? 1u : 0u ) ), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
+                      ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
+                      ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep, order, kscnt, hidx,
+                      (uint4 const *)( ks ? ctx->d_htab : NULL ), (uint4 const *)( ks ? ctx->d_btabh : NULL ) );
+  if( ctx->timing ) hipEventRecord( b.ev[2], st );
+  hipLaunchKernelGGL( ( fold ? fd_dsm_slow_kernel<1> : fd_dsm_slow_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, nsig,
+                      ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt,
+                      nsb * FD_WG, arep, order );
+  return 0;
+}
+
+/* Full-length throughput path (half = 0): fd_decode_kernel (A only), fd_hash_kernel, fd_table_kernel, the walk
+   fd_dsm_kernel, which leaves P for the deferred R check: fd_rprod_kernel, fd_rinv_kernel, fd_rcheck_kernel and
+   fd_rslow_kernel. */
+static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
+  u32 nsig = b.nsig; unsigned sg = b.sg; i8 * code = b.code; hipStream_t st = b.st;
+  u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW );
+  hipLaunchKernelGGL( fd_decode_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig, 0,
+                      ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
+                      (u32 *)NULL, (unsigned char *)NULL, 0u );
+  hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig,
+                      ctx->semantics, 1, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
+                      (uint4 const *)ctx->d_khash );
+  hipLaunchKernelGGL( fd_table_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics,
+                      (unsigned char const *)NULL, code, ctx->d_Axy, ctx->d_tab );
+  if( ctx->timing ) hipEventRecord( b.ev[1], st );
+  /* no carry fold up to nofold_max (<= 2 waves per SIMD: latency-bound, independent column chains) */
+  hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
+                      nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 1 );
+  if( ctx->timing ) hipEventRecord( b.ev[2], st );
+  hipLaunchKernelGGL( fd_rprod_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_P, ctx->d_O, ctx->d_blk, slow_cnt );
+  hipLaunchKernelGGL( fd_rinv_kernel, dim3((sg + FD_WG - 1)/FD_WG), dim3(FD_WG), 0, st, sg, ctx->d_blk );
+  hipLaunchKernelGGL( fd_rcheck_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_Rxy, ctx->d_P, ctx->d_O, ctx->d_blk,
+                      ctx->d_slow, slow_cnt );
+  hipLaunchKernelGGL( fd_rslow_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, code, ctx->d_Rxy, ctx->d_P,
+                      ctx->d_slow, slow_cnt );
+  return 0;
+}
+
+/* flags: 1 = the map is written already (fused into fd_parse_kernel), 2 = no reduce (fd_finish_kernel does it) */
 static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payload, fdgpu_txn_desc_t const * d_desc,
                          unsigned long txn_cnt, unsigned long sig_cnt, i8 * d_txn_out, i8 * d_sig_out, hipStream_t st,
                          unsigned char const * d_pflag = NULL, int flags = 0 ) {
   if( !txn_cnt ) return 0;
-  i8 * code = d_sig_out ? d_sig_out : ctx->d_code;
-  hipEvent_t * ev = ctx->ev;
-  if( ctx->timing ) { ev = ctx->ring[ ctx->ring_cnt % fdgpu_ed25519_ctx_t::NRING ]; ctx->ring_cnt++; }
-  u32 nsig = (u32)sig_cnt;
+  fd_batch b = { d_payload, d_desc, (u32)sig_cnt, (unsigned)( (sig_cnt + FD_WG - 1) / FD_WG ),
+                 d_sig_out ? d_sig_out : ctx->d_code, st, ctx->ev };
+  if( ctx->timing ) { b.ev = ctx->ring[ ctx->ring_cnt % fdgpu_ed25519_ctx_t::NRING ]; ctx->ring_cnt++; }
   unsigned tg = (unsigned)( (txn_cnt + FD_WG - 1) / FD_WG );
-  unsigned sg = (unsigned)( (sig_cnt + FD_WG - 1) / FD_WG );
-  ctx->last_path = FDGPU_PATH_NONE;
-  if( nsig ) {
+  ctx->last_path = pick_path( ctx, b.nsig );
+  if( b.nsig ) {
     if( !( flags & 1 ) )
-      hipLaunchKernelGGL( fd_expand_kernel, dim3(tg), dim3(FD_WG), 0, st, d_desc, (u32)txn_cnt, ctx->d_map, nsig,
-                          ctx->d_slow + ctx->max_sig );
-    if( ctx->timing ) hipEventRecord( ev[0], st );
-    /* small batch: cannot fill the GPU, so latency is the sum of the kernels' per-wave
-       instruction streams -- decode A, decode R and hash side by side in one launch,
-       R compared at the end of the DSM (no R-check chain and its inversion) */
-    int small = nsig <= ctx->small_max, lanes = 1;
-    int hs = ctx->half && small;               /* half-size scalars on the latency path */
-    int half = ctx->half && !small;            /* ... on the throughput path */
-    int defer = FD_DEFER_R && !small && !half;
-    if( small ) {
-      lanes = pick_path( ctx, nsig );
-      ctx->last_path = lanes;
-      int d2 = lanes > 1;
-      int qs = hs && ctx->quad_sha >= 0 && nsig <= FD_QSHA_MAX;   /* the hash role on quads (fd_sha512_RAM_quad) */
-      if( qs )
-        hipLaunchKernelGGL( (fd_prep_kernel<0,1,1>), dim3(6*sg), dim3(FD_WG), ctx->excl_lds[7], st, d_payload, d_desc, ctx->d_map, nsig,
-                            (u32)sg, ctx->semantics, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, code, ctx->d_digA, ctx->d_digB,
-                            ctx->d_tab, (uint4 const *)ctx->d_khash, ctx->d_tabR, ctx->d_digR, ctx->d_slow,
-                            ctx->d_slow + ctx->max_sig, ctx->half_force_slow, ctx->d_htop );
-      else if( hs )      /* half-size: the A and R lanes build both tables, the hash lane (c0, c1, s') */
-        hipLaunchKernelGGL( (fd_prep_kernel<0,1>), dim3(3*sg), dim3(FD_WG), ctx->excl_lds[0], st, d_payload, d_desc, ctx->d_map, nsig,
-                            (u32)sg, ctx->semantics, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, code, ctx->d_digA, ctx->d_digB,
-                            ctx->d_tab, (uint4 const *)ctx->d_khash, ctx->d_tabR, ctx->d_digR, ctx->d_slow,
-                            ctx->d_slow + ctx->max_sig, ctx->half_force_slow, ctx->d_htop );
-      else {
-        hipLaunchKernelGGL( (fd_prep_kernel<0,0>), dim3(3*sg), dim3(FD_WG), ctx->excl_lds[1], st, d_payload, d_desc, ctx->d_map, nsig,
-                            (u32)sg, ctx->semantics, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, code, ctx->d_digA, ctx->d_digB,
-                            d2 ? ctx->d_tab : (uint4 *)NULL, (uint4 const *)ctx->d_khash, (uint4 *)NULL, (i8 *)NULL,
-                            (u32 *)NULL, (u32 *)NULL, 0u, (unsigned char *)NULL );
-        if( !d2 )
-          hipLaunchKernelGGL( fd_table_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, ctx->d_pstat, code,
-                              ctx->d_Axy, ctx->d_tab );
-      }
-    } else if( half ) {
-      ctx->last_path = FDGPU_PATH_THROUGHPUT;
-      /* half-size scalars: decode A and R, result codes + hash + (c0, c1, s'), both tables */
-      unsigned pg = (unsigned)( ( 2UL*sig_cnt + FD_WG - 1) / FD_WG );
-#if FD_HALF_FUSED_TABLE
-      if( ctx->key_dedup ) {
-        /* each distinct key decoded once: the table cleared for this batch -- the smallest power of two of
-           slots that is twice its signatures, so a small batch on a large context clears little -- then A
-           lanes over the representatives, R lanes over every signature */
-        u32 slots = 64u;
-        if( !ctx->kd_tiny ) while( slots < ctx->kd_slots && slots < 2u*nsig ) slots <<= 1;
-        HIPCHK( hipMemsetAsync( ctx->d_ktab, 0, (size_t)slots * sizeof(u32), st ), -3 );
-        if( ctx->key_split ) {
-          /* repeated keys: count the signatures per key, then partition the batch into hot and cold */
-          HIPCHK( hipMemsetAsync( ctx->d_kcnt, 0, (size_t)nsig * sizeof(u32), st ), -3 );
-          hipLaunchKernelGGL( fd_keydedup_kernel<1>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
-                              ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep, ctx->d_ulist,
-                              ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ), ctx->d_kcnt, ctx->hot_min );
-          hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
-                              (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
-                              ctx->d_slow + ctx->max_sig + 4, ctx->hot_cap );
-        } else
-        hipLaunchKernelGGL( fd_keydedup_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
-                            ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep, ctx->d_ulist,
-                            ctx->d_slow + ctx->max_sig + 1, ctx->d_pstat, FD_KD_SBLK( sg ), (u32 *)NULL, 0u );
-        hipLaunchKernelGGL( fd_decode_kernel, dim3(2*sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
-                            ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR, (u32 const *)ctx->d_ulist,
-                            ctx->d_slow + ctx->max_sig + 1, ctx->d_astat, (u32)sg );
-      } else
-      hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR, (u32 const *)NULL,
-                          (u32 *)NULL, (unsigned char *)NULL, 0u );
-#else
-      hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, 1,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
-                          (u32 *)NULL, (unsigned char *)NULL, 0u );
-#endif
-      if( ctx->timing ) hipEventRecord( ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
-      uint4 const * kh = (uint4 const *)ctx->d_khash;
-      if( FD_SHA_SPLIT && !kh ) {
-        hipLaunchKernelGGL( fd_sha_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, ctx->d_kdig );
-        kh = ctx->d_kdig;
-      }
-      if( ctx->key_split ) {
-        /* the high tables of the hot keys in the first blocks (two lanes per key, the worst case of nsig / hot_min
-           keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
-        unsigned hb = (unsigned)( ( 2UL * ( sig_cnt / ctx->hot_min ) + FD_WG - 1 ) / FD_WG );
-        hipLaunchKernelGGL( fd_hashh_kernel<1>, dim3(hb + sg + 1), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
-                            ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_slow,
-                            ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop,
-                            (u32 const *)ctx->d_arep, (unsigned char const *)ctx->d_astat, (u32 const *)ctx->d_order,
-                            (u32 const *)( ctx->d_slow + ctx->max_sig + 4 ), (u32 const *)ctx->d_hlist,
-                            (uint4 const *)ctx->d_Axy, ctx->d_htab, (u32)hb );
-      } else
-      hipLaunchKernelGGL( fd_hashh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
-                          ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR, ctx->d_digB, ctx->d_slow,
-                          ctx->d_slow + ctx->max_sig, kh, ctx->half_force_slow, ctx->d_htop,
-                          (u32 const *)( ctx->key_dedup ? ctx->d_arep : NULL ),
-                          (unsigned char const *)( ctx->key_dedup ? ctx->d_astat : NULL ), (u32 const *)NULL,
-                          (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 *)NULL, 0u );
-#if !FD_HALF_FUSED_TABLE
-      hipLaunchKernelGGL( fd_tableh_kernel, dim3(2*sg), dim3(FD_WG), 0, st, nsig, (u32)sg, code, ctx->d_Axy, ctx->d_Rxy,
-                          ctx->d_tab, ctx->d_tabR );
-#endif
-    } else {
-      ctx->last_path = FDGPU_PATH_THROUGHPUT_FULL;
-      unsigned pg = (unsigned)( ( (defer ? 1UL : 2UL)*sig_cnt + FD_WG - 1) / FD_WG );
-      hipLaunchKernelGGL( fd_decode_kernel, dim3(pg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig, !defer,
-                          ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
-                          (u32 *)NULL, (unsigned char *)NULL, 0u );
-      hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, d_payload, d_desc, ctx->d_map, nsig,
-                          ctx->semantics, defer, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
-                          (uint4 const *)ctx->d_khash );
-      hipLaunchKernelGGL( fd_table_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics,
-                          (unsigned char const *)NULL, code, ctx->d_Axy, ctx->d_tab );
-    }
-    if( ctx->timing ) hipEventRecord( ev[1], st );
-    if( small && lanes==8 )
-      hipLaunchKernelGGL( fd_dsm8_kernel<0>, dim3(8*sg), dim3(FD_WG), ctx->excl_lds[2], st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
-                          ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->semantics, ctx->d_pstat,
-                          ctx->d_htop, ctx->d_Rxy, ctx->d_slow, ctx->d_slow + ctx->max_sig );
-    else if( small && lanes==4 )
-      hipLaunchKernelGGL( (hs ? fd_dsm4_kernel<0,1> : fd_dsm4_kernel<0,0>), dim3(4*sg), dim3(FD_WG),
-                          ctx->excl_lds[ hs ? 3 : 4 ], st, nsig, ctx->d_tab,
-                          ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->semantics, ctx->d_pstat,
-                          ctx->d_tabR, ctx->d_digR, ctx->d_btab2, ctx->d_htop, ctx->d_slow, ctx->d_slow + ctx->max_sig );
-    else if( small && lanes==2 )
-      hipLaunchKernelGGL( (hs ? fd_dsm2_kernel<0,1> : fd_dsm2_kernel<0,0>), dim3(2*sg), dim3(FD_WG),
-                          ctx->excl_lds[ hs ? 5 : 6 ], st, nsig, ctx->d_tab,
-                          ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->semantics, ctx->d_pstat,
-                          ctx->d_tabR, ctx->d_digR, ctx->d_btab2, ctx->d_htop, ctx->d_slow, ctx->d_slow + ctx->max_sig );
-    else if( hs )                              /* one lane: the half-size walk, result codes at its start */
-      hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
-                          ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow,
-                          ctx->d_slow + ctx->max_sig, 0u, ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL,
-                          (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL );
-    else if( half ) {
-      /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the
-         rest (if any) in fd_dsm_slow_kernel */
-      unsigned nsb = ( sg + 63u ) / 64u;
-      u32 * slow_cnt = ctx->d_slow + ctx->max_sig;
-      u32 const * arep = ctx->key_dedup ? ctx->d_arep : NULL;     /* -A's tables at the representatives */
-      /* repeated keys: lane i <-> signature order[i], hot blocks then cold blocks (at most sg + 1 of them) */
-      int ks = ctx->key_split;
-      u32 const * order = ks ? ctx->d_order : NULL, * kscnt = ks ? ctx->d_slow + ctx->max_sig + 4 : NULL;
-      u32 const * hidx = ks ? ctx->d_hidx : NULL;
-      uint4 const * htab = ks ? ctx->d_htab : NULL, * btabh = ks ? ctx->d_btabh : NULL;
-      unsigned wg = nsb + sg + ( ks ? 1u : 0u );
-      int fold = nsig > ctx->nofold_max;
-      hipLaunchKernelGGL( ( fold ? ( ks ? fd_dsmh_kernel<1,1> : fd_dsmh_kernel<1,0> )
-                                 : ( ks ? fd_dsmh_kernel<0,1> : fd_dsmh_kernel<0,0> ) ),
-                          dim3(wg), dim3(FD_WG), fold ? FD_DSMH_LDS : 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
-                          ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
-                          ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep, order, kscnt, hidx, htab, btabh );
-      if( ctx->timing ) hipEventRecord( ev[2], st );
-      hipLaunchKernelGGL( ( fold ? fd_dsm_slow_kernel<1> : fd_dsm_slow_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, nsig,
-                          ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt,
-                          nsb * FD_WG, arep, order );
-    }
-    else if( nsig <= ctx->nofold_max )         /* <= 2 waves per SIMD: latency-bound, independent column chains */
-      hipLaunchKernelGGL( fd_dsm_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy,
-                          ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, defer );
-    else
-      hipLaunchKernelGGL( fd_dsm_kernel<1>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy,
-                          ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, defer );
-    if( ctx->timing && !half ) hipEventRecord( ev[2], st );
-    if( hs && !( small && lanes > 1 ) )        /* slow list (normally empty); the 8/4/2-lane walks ran it */
-      hipLaunchKernelGGL( fd_dsm_slowl_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA,
-                          ctx->d_digB, ctx->d_btab, code, ctx->d_slow, ctx->d_slow + ctx->max_sig, ctx->semantics,
-                          ctx->d_pstat );
-    if( defer ) {
-      u32 * slow_cnt = ctx->d_slow + ctx->max_sig;
-      hipLaunchKernelGGL( fd_rprod_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_P, ctx->d_O, ctx->d_blk, slow_cnt );
-      hipLaunchKernelGGL( fd_rinv_kernel, dim3((sg + FD_WG - 1)/FD_WG), dim3(FD_WG), 0, st, sg, ctx->d_blk );
-      hipLaunchKernelGGL( fd_rcheck_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_Rxy, ctx->d_P, ctx->d_O, ctx->d_blk,
-                          ctx->d_slow, slow_cnt );
-      hipLaunchKernelGGL( fd_rslow_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, code, ctx->d_Rxy, ctx->d_P,
-                          ctx->d_slow, slow_cnt );
-    }
+      hipLaunchKernelGGL( fd_expand_kernel, dim3(tg), dim3(FD_WG), 0, st, d_desc, (u32)txn_cnt, ctx->d_map, b.nsig,
+                          slow_word( ctx, FD_SW_SLOW ) );
+    if( ctx->timing ) hipEventRecord( b.ev[0], st );
+    int err = b.nsig <= ctx->small_max ? launch_latency( ctx, b, ctx->last_path )
+            : ctx->half                ? launch_half( ctx, b ) : launch_full( ctx, b );
+    if( err ) return err;
   }
   if( !( flags & 2 ) )
-    hipLaunchKernelGGL( fd_reduce_kernel, dim3(tg), dim3(FD_WG), 0, st, d_desc, (u32)txn_cnt, nsig, code, d_pflag, d_txn_out );
-  if( ctx->timing ) hipEventRecord( ev[3], st );
+    hipLaunchKernelGGL( fd_reduce_kernel, dim3(tg), dim3(FD_WG), 0, st, d_desc, (u32)txn_cnt, b.nsig, b.code, d_pflag, d_txn_out );
+  if( ctx->timing ) hipEventRecord( b.ev[3], st );
   HIPCHK( hipGetLastError(), -3 );
   return 0;
 }
@@ -3327,11 +3050,8 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   HIPCHK( hipMalloc( &ctx->d_P, ns * 30 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_O, ns * 10 * sizeof(u32) ), -1 );
   HIPCHK( hipMalloc( &ctx->d_blk, ( ( ns + FD_WG - 1 ) / FD_WG ) * 10 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + 8 ) * sizeof(u32) ), -1 );   /* + the slow count, the distinct-key count, whether
-                                                                           most keys of the last batch were distinct, the
-                                                                           sample's count (fd_keydedup_kernel), and the hot
-                                                                           keys, hot and cold signatures (fd_keysplit_kernel) */
-  HIPCHK( hipMemsetAsync( ctx->d_slow + ns, 0, 8 * sizeof(u32), ctx->stream ), -1 );
+  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + FD_SW_CNT ) * sizeof(u32) ), -1 );   /* the list + the batch's counts (slow_word) */
+  HIPCHK( hipMemsetAsync( slow_word( ctx, 0 ), 0, FD_SW_CNT * sizeof(u32), ctx->stream ), -1 );
   fdgpu_debug_opts_t dbg; debug_opts_get( &dbg );   /* test / A/B choices (fdgpu_debug_set_opts), never the environment */
   ctx->half = dbg.half >= 0 ? dbg.half : FD_HALF;
   ctx->half_force_slow = dbg.half_force_slow;
@@ -3339,10 +3059,9 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
     HIPCHK( hipMalloc( &ctx->d_tabR, ns * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
     HIPCHK( hipMalloc( &ctx->d_digR, ns * FD_HDIG ), -1 );
     HIPCHK( hipMalloc( &ctx->d_htop, ns ), -1 );
-    if( FD_SHA_SPLIT ) HIPCHK( hipMalloc( &ctx->d_kdig, ns * 4 * sizeof(uint4) ), -1 );
     HIPCHK( hipMalloc( &ctx->d_btab2, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
-    /* distinct keys decoded once (needs the decode lanes to build the tables: FD_HALF_FUSED_TABLE) */
-    ctx->key_dedup = FD_HALF_FUSED_TABLE && dbg.key_dedup != 1;
+    /* distinct keys decoded once (the decode lanes build the tables) */
+    ctx->key_dedup = dbg.key_dedup != 1;
     if( ctx->key_dedup ) {
       unsigned long slots = 64UL;                    /* fdgpu_debug_opts_t.key_dedup = 2 (tests): 64 slots, 2 probes */
       if( dbg.key_dedup != 2 ) while( slots < 2UL*ns && slots < ( 1UL << 31 ) ) slots <<= 1;
@@ -3439,7 +3158,6 @@ fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx ) {
   (void)hipFree( ctx->d_Rxy ); (void)hipFree( ctx->d_Axy ); (void)hipFree( ctx->d_digA ); (void)hipFree( ctx->d_digB );
   (void)hipFree( ctx->d_btab ); (void)hipFree( ctx->d_rdesc ); (void)hipFree( ctx->d_pflag );
   (void)hipFree( ctx->d_tabR ); (void)hipFree( ctx->d_digR ); (void)hipFree( ctx->d_htop ); (void)hipFree( ctx->d_btab2 );
-  (void)hipFree( ctx->d_kdig );
   (void)hipFree( ctx->d_ktab ); (void)hipFree( ctx->d_arep ); (void)hipFree( ctx->d_ulist ); (void)hipFree( ctx->d_astat );
   (void)hipFree( ctx->d_kcnt ); (void)hipFree( ctx->d_hidx ); (void)hipFree( ctx->d_hlist ); (void)hipFree( ctx->d_order );
   (void)hipFree( ctx->d_htab ); (void)hipFree( ctx->d_btabh );
@@ -3514,25 +3232,6 @@ fd_mad_probe_kernel( u32 iters, u32 seed, u64 * out ) {
   for( int i=0; i<16; i++ ) x ^= acc[i];
   if( x == 0x1234567ull ) out[0] = x;
 }
-
-#if FD_CLOCK_PROBE
-/* mean shader clock (MHz) over the blocks of the last fd_dsm_kernel launch
-   that recorded (sum of s_memtime deltas / sum of s_memrealtime deltas x
-   100 MHz), and those blocks' count */
-extern "C" double
-fdgpu_debug_dsm_clock_mhz( unsigned long nblocks, unsigned long * recorded ) {
-  static unsigned long long h[ FD_CLK_BLOCKS ][ 4 ];
-  if( nblocks > FD_CLK_BLOCKS ) nblocks = FD_CLK_BLOCKS;
-  if( hipMemcpyFromSymbol( h, HIP_SYMBOL( fd_clk_buf ), nblocks * 4 * sizeof(unsigned long long) ) != hipSuccess ) return -1.;
-  double dc = 0., dr = 0.; unsigned long k = 0;
-  for( unsigned long b=0; b<nblocks; b++ ) {
-    if( h[b][3] <= h[b][2] || h[b][1] <= h[b][0] ) continue;
-    dc += (double)( h[b][1] - h[b][0] ); dr += (double)( h[b][3] - h[b][2] ); k++;
-  }
-  *recorded = k;
-  return dr > 0. ? dc / dr * 100. : -1.;
-}
-#endif
 
 extern "C" double
 fdgpu_mad_peak_per_s( int device ) {
@@ -3841,7 +3540,7 @@ static int launch_raw( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payloa
   }
   hipLaunchKernelGGL( fd_parse_kernel, dim3(g), dim3(FD_WG), 0, st, d_payload, d_raw, (u32)txn_cnt,
                       ctx->d_rdesc, ctx->d_pflag, d_img, (u32)img_stride, d_fp, ds, d_dtag, d_ovr,
-                      fused ? ctx->d_map : (u32 *)NULL, (u32)sig_cnt, fused ? ctx->d_slow + ctx->max_sig : (u32 *)NULL,
+                      fused ? ctx->d_map : (u32 *)NULL, (u32)sig_cnt, fused ? slow_word( ctx, FD_SW_SLOW ) : (u32 *)NULL,
                       stamp );
   HIPCHK( hipGetLastError(), -3 );
   return launch_batch( ctx, d_payload, ctx->d_rdesc, txn_cnt, sig_cnt, d_txn_out, NULL, st, ctx->d_pflag,
@@ -4899,7 +4598,7 @@ fdgpu_ed25519_slow_count( fdgpu_ed25519_ctx_t * ctx ) {
   if( !ctx || !ctx->half ) return 0UL;
   if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return ~0UL;
   u32 cnt = 0u;
-  if( hipMemcpy( &cnt, ctx->d_slow + ctx->max_sig, sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
+  if( hipMemcpy( &cnt, slow_word( ctx, FD_SW_SLOW ), sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
   return (unsigned long)cnt;
 }
 
@@ -4908,7 +4607,7 @@ fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx ) {
   if( !ctx || !ctx->half || !ctx->key_dedup || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0UL;
   if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return ~0UL;
   u32 cnt = 0u;
-  if( hipMemcpy( &cnt, ctx->d_slow + ctx->max_sig + 1, sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
+  if( hipMemcpy( &cnt, slow_word( ctx, FD_SW_KEYS ), sizeof(u32), hipMemcpyDeviceToHost ) != hipSuccess ) return ~0UL;
   return (unsigned long)cnt;
 }
 
@@ -4919,7 +4618,7 @@ fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, un
   if( !ctx || !ctx->half || !ctx->key_split || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
   if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
   u32 cnt[ 2 ] = { 0u, 0u };
-  if( hipMemcpy( cnt, ctx->d_slow + ctx->max_sig + 4, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ), sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
   if( hot_keys ) *hot_keys = (unsigned long)cnt[0];
   if( hot_sigs ) *hot_sigs = (unsigned long)cnt[1];
   return 0;

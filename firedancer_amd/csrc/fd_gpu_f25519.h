@@ -55,9 +55,7 @@ FD_DEV u64 fd_mad_a( u32 a, u32 b, u64 c ) {
    scheduler from hoisting the next operation's operand preparation into
    this one's carry chain, which otherwise inflates register pressure
    several-fold on long dependent chains (pow22523: 256 -> ~110 VGPRs). */
-#ifndef FD_SCHED_FENCE
 #define FD_SCHED_FENCE() __builtin_amdgcn_sched_barrier( 0 )
-#endif
 
 #define FE_W(i)    ( ((i) & 1) ? 25 : 26 )
 #define FE_M(i)    ( ((i) & 1) ? 0x1ffffffu : 0x3ffffffu )
@@ -156,9 +154,7 @@ FD_DEV void fe_carry64( fe & r, u64 h[ 10 ] ) {
    signatures) finishes sooner with ten independent column chains (F = 0:
    more instructions, more VGPRs, 4x the ILP) -- profiles/r02/dsm_ab.  The
    multiply family below is templated on F; FD_CARRY_FOLD is the default. */
-#ifndef FD_CARRY_FOLD
 #define FD_CARRY_FOLD 1
-#endif
 template<int F> FD_DEV u64 fd_col_mad( u32 a, u32 b, u64 c ) {
   if constexpr( F != 0 ) return fd_mad_a( a, b, c );
   else                   return fd_mad( a, b, c );
@@ -175,34 +171,6 @@ template<int F> FD_DEV u64 fd_col_mad( u32 a, u32 b, u64 c ) {
     r.v[0] = (u32)t0_ & FE_M(0); r.v[1] += (u32)( t0_ >> 26 );                \
   } while(0)
 
-/* FD_FOLD4: four chains (columns 0-2, 3-4, 5-7, 8-9) instead of two: twice the independent
-   accumulators, so consecutive multiply-adds of one chain are further apart (no wait state between
-   them), for two more carry junctions (limbs 3 and 8).  A/B knob. */
-#ifndef FD_FOLD4
-#define FD_FOLD4 0
-#endif
-#define FE_FOLD_CHAINS4( r, COL, ca, cb ) do {                              \
-    u64 cc = 0, cd = 0;                                                      \
-    _Pragma("unroll") for( int t_=0; t_<3; t_++ ) {                          \
-      COL( t_, ca );     r.v[t_]   = (u32)ca & FE_M(t_);   ca >>= FE_W(t_);  \
-      if( t_ < 2 ) { COL( t_+3, cb ); r.v[t_+3] = (u32)cb & FE_M(t_+3); cb >>= FE_W(t_+3); } \
-      COL( t_+5, cc );   r.v[t_+5] = (u32)cc & FE_M(t_+5); cc >>= FE_W(t_+5);\
-      if( t_ < 2 ) { COL( t_+8, cd ); r.v[t_+8] = (u32)cd & FE_M(t_+8); cd >>= FE_W(t_+8); } \
-    }                                                                        \
-    u64 t3_ = fd_add32( ca, r.v[3] );                                        \
-    r.v[3] = (u32)t3_ & FE_M(3); r.v[4] += (u32)( t3_ >> 25 );                \
-    u64 t5_ = fd_add32( cb, r.v[5] );                                        \
-    r.v[5] = (u32)t5_ & FE_M(5); r.v[6] += (u32)( t5_ >> 25 );                \
-    u64 t8_ = fd_add32( cc, r.v[8] );                                        \
-    r.v[8] = (u32)t8_ & FE_M(8); r.v[9] += (u32)( t8_ >> 26 );                \
-    u64 t0_ = (u64)r.v[0] + cd * 19u;                                        \
-    r.v[0] = (u32)t0_ & FE_M(0); r.v[1] += (u32)( t0_ >> 26 );                \
-  } while(0)
-#if FD_FOLD4
-#undef  FE_FOLD_CHAINS
-#define FE_FOLD_CHAINS FE_FOLD_CHAINS4
-#endif
-
 /* Operand multiples are formed only for the limbs that use them, each
    behind an empty asm so the compiler keeps one register per multiple
    instead of re-deriving it at every use (VALU-issue bound: every
@@ -212,35 +180,16 @@ template<int F> FD_DEV u64 fd_col_mad( u32 a, u32 b, u64 c ) {
 /* 2x as x + x: on gfx950 v_add_u32 issues in 2.9 cycles per wave64 and
    v_lshlrev_b32 (what the compiler emits for 2x) in 4.75 (tools/instprobe,
    profiles/r02/roofline/instprobe.log); the asm also keeps the multiple in
-   one register like FD_KEEP.  FD_ADD2=0: the compiler's shift. */
-#ifndef FD_ADD2
-#define FD_ADD2 1
-#endif
+   one register like FD_KEEP. */
 FD_DEV u32 fd_x2( u32 x ) {
-#if FD_ADD2
   u32 r; asm( "v_add_u32 %0, %1, %1" : "=v"( r ) : "v"( x ) ); return r;
-#else
-  u32 r = 2u * x; FD_KEEP( r ); return r;
-#endif
 }
 
-/* acc + x for a 32-bit x.  FD_MAD1=1: as one v_mad_u64_u32 (x * 1 + acc, 4.66 cycles isolated)
-   instead of zero-extending x (v_mov_b32) and a 64-bit add (v_lshl_add_u64, 7.5 cycles together).
-   Off: the DSM's time follows its multiply-add count more than its other instructions (27 more
-   v_mad_u64_u32 per doubling measured 0.3 % slower, four carry chains with ~14 more 2.5-4 % slower,
-   profiles/r02/dsm_ab), so the add stays off the multiplier. */
-#ifndef FD_MAD1
-#define FD_MAD1 0
-#endif
-FD_DEV u64 fd_add32( u64 acc, u32 x ) {
-#if FD_MAD1
-  u64 r, cy;   /* (the compiler folds a C multiply by 1 back into the add: spell the instruction) */
-  asm( "v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"( r ), "=s"( cy ) : "v"( x ), "v"( acc ) );
-  return r;
-#else
-  return acc + (u64)x;
-#endif
-}
+/* acc + x for a 32-bit x: x zero-extended (v_mov_b32) and a 64-bit add (v_lshl_add_u64, 7.5 cycles together).
+   Not one v_mad_u64_u32 (x * 1 + acc, 4.66 cycles isolated): the DSM's time follows its multiply-add count more
+   than its other instructions (27 more v_mad_u64_u32 per doubling measured 0.3 % slower, four carry chains
+   with ~14 more 2.5-4 % slower, profiles/r02/dsm_ab), so the add stays off the multiplier. */
+FD_DEV u64 fd_add32( u64 acc, u32 x ) { return acc + (u64)x; }
 
 /* 19 g_j for j = 1..9 (the wrapped columns of a product with g) */
 struct fe19 { u32 v[10]; };
@@ -368,15 +317,12 @@ FD_DEV void fe_sqr_sub( fe & r, fe const & f, fe const & b ) {
   FD_SCHED_FENCE();
 }
 
-/* r = 2 f^2 + 4p - b (b L) -> T.  FD_SQR2_PRE: f must be T (every caller
+/* r = 2 f^2 + 4p - b (b L) -> T.  f must be T (every caller
    passes a point's Z straight from a multiply); the factor 2 rides in the
    operands -- multiples f, 2f, 4f (limbs 1, 3), 38f (even j >= 6) and 76f
    (odd j >= 5), all < 2^31.3 for T limbs -- so each column accumulates into
    the carry chain directly instead of a separate sum doubled into it
    (v_lshl_add_u64 per column).  Column sums stay < 2^62. */
-#ifndef FD_SQR2_PRE
-#define FD_SQR2_PRE 1
-#endif
 #define FE_SQR2_OPERANDS( f )                                                 \
   u32 g2[10], g4[4], gw[10];                                                  \
   _Pragma("unroll") for( int i=0; i<10; i++ ) g2[i] = fd_x2( f.v[i] );        \
@@ -410,7 +356,6 @@ FD_DEV void fe_sqr_sub( fe & r, fe const & f, fe const & b ) {
 
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void fe_sqr2_sub( fe & r, fe const & f, fe const & b ) {
-#if FD_SQR2_PRE
   FE_SQR2_OPERANDS( f );
   if constexpr( FM != 0 ) {
 #define FE_SQR2P_SUB_COL( k, acc ) do { acc = fd_add32( acc, FE_4P(k) - b.v[k] ); FE_SQR2_COL( k, acc ); } while(0)
@@ -424,21 +369,6 @@ FD_DEV void fe_sqr2_sub( fe & r, fe const & f, fe const & b ) {
     for( int k=0; k<10; k++ ) { u64 acc = (u64)( FE_4P(k) - b.v[k] ); FE_SQR2_COL( k, acc ); h[k] = acc; }
     fe_carry64( r, h );
   }
-#else
-  FE_SQR_OPERANDS( f );
-  if constexpr( FM != 0 ) {
-#define FE_SQR2_SUB_COL( k, acc ) do { u64 h_ = 0; FE_SQR_COL( k, h_ ); acc = ( h_ << 1 ) + acc + (u64)( FE_4P(k) - b.v[k] ); } while(0)
-    u64 ca = 0, cb = 0; fe o;
-    FE_FOLD_CHAINS( o, FE_SQR2_SUB_COL, ca, cb );
-    r = o;
-#undef FE_SQR2_SUB_COL
-  } else {
-    u64 h[10];
-#pragma unroll
-    for( int k=0; k<10; k++ ) { u64 acc = 0; FE_SQR_COL( k, acc ); h[k] = ( acc << 1 ) + (u64)( FE_4P(k) - b.v[k] ); }
-    fe_carry64( r, h );
-  }
-#endif
   FD_SCHED_FENCE();
 }
 

@@ -1,7 +1,7 @@
 #!/bin/bash
-# A/B of field-arithmetic instruction choices (fd_gpu_f25519.h FD_ADD2 / FD_MAD1 / FD_SQR2_PRE) on the
-# HBM-resident configs[1] bench: sigs/s and per-kernel ms for each build/ab/<variant>.so, interleaved
-# twice to expose drift.  Build first (CPU): tools/ab_build.sh <variant> -DFD_...=0 ...
+# A/B of engine builds on the HBM-resident configs[1] bench (first used for the field-arithmetic
+# instruction choices of fd_gpu_f25519.h): sigs/s and per-kernel ms for each build/ab/<variant>.so,
+# interleaved twice to expose drift.  Build first (CPU): tools/ab_build.sh <variant> [hipcc flags]
 # usage (GPU box): bash tools/dsm_ab.sh <variant> ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/dsm_ab
