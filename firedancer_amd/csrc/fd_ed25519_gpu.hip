@@ -327,8 +327,26 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
   if( tabA && ( *st & 3u )==0u ) atab_build( is_r ? tabR : tabA, s, is_r ? Rxy : Axy );
 }
 
-/* Signed digits of k (radix 16, digA[64][n]) and S (radix 2^FD_BWIN,
-   digB[FD_BDIG][n]), stored coalesced. */
+/* Signed digits of the base point's scalar Sw (radix 2^FD_BWIN, digB[FD_BDIG][n]) in column s.  Returns top
+   raised to the highest window win( i ) at which a walk adds a nonzero digit i (the half-size walks start at
+   their wave's top window). */
+template<class W>
+FD_DEV int store_digits_B( u32 const Sw[ 8 ], u32 s, size_t n, short * __restrict__ digB, int top, W win ) {
+  int carry = 0;
+#pragma unroll
+  for( int i=0; i<FD_BDIG; i++ ) {
+    int bit = FD_BWIN*i;
+    int v = (int)((Sw[bit>>5] >> (bit&31)) & ((1u<<FD_BWIN)-1u)) + carry;
+    carry = (v + (1<<(FD_BWIN-1))) >> FD_BWIN;
+    int db = v - (carry << FD_BWIN);
+    digB[(size_t)i*n + s] = (short)db;
+    int wb = win( i );
+    top = ( db && wb > top ) ? wb : top;
+  }
+  return top;
+}
+
+/* Signed digits of k (radix 16, digA[64][n]) and S (digB), stored coalesced. */
 FD_DEV void store_digits( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 s, size_t n,
                           i8 * __restrict__ digA, short * __restrict__ digB ) {
   int carry = 0;
@@ -338,14 +356,7 @@ FD_DEV void store_digits( u32 const k[ 8 ], u32 const Sw[ 8 ], u32 s, size_t n,
     carry = (v + 8) >> 4;
     digA[(size_t)i*n + s] = (i8)(v - (carry << 4));
   }
-  carry = 0;
-#pragma unroll
-  for( int i=0; i<FD_BDIG; i++ ) {
-    int bit = FD_BWIN*i;
-    int v = (int)((Sw[bit>>5] >> (bit&31)) & ((1u<<FD_BWIN)-1u)) + carry;
-    carry = (v + (1<<(FD_BWIN-1))) >> FD_BWIN;
-    digB[(size_t)i*n + s] = (short)(v - (carry << FD_BWIN));
-  }
+  (void)store_digits_B( Sw, s, n, digB, 0, []( int ) { return 0; } );   /* (the full-length walks take every window) */
 }
 
 /* ---- half-size scalars (fd_gpu_lattice.h) ------------------------------ */
@@ -431,22 +442,12 @@ FD_DEV void hs_store_digits( u32 const c0[ 5 ], u32 const c1m[ 5 ], int c1neg, u
     digR[(size_t)i*n + s] = (i8)( c1neg ? -dr : dr );
     top = ( da | dr ) ? i : top;
   }
-  int carry = 0;
-#pragma unroll
-  for( int i=0; i<FD_BDIG; i++ ) {
-    int bit = FD_BWIN*i;
-    int v = (int)((sp[bit>>5] >> (bit&31)) & ((1u<<FD_BWIN)-1u)) + carry;
-    carry = (v + (1<<(FD_BWIN-1))) >> FD_BWIN;
-    int db = v - (carry << FD_BWIN);
-    digB[(size_t)i*n + s] = (short)db;
-    /* the walks add s' digit i at window 4i (i < 8) or 4(i-8)+2 (i >= 8, the 2^120 B table): the top
-       window counts these too.  (Round 4 took it from c0 / c1 alone; a wave whose pending signatures all
-       had c0, c1 < 2^120 -- ~7.5e-6 of hash-distributed k, alone in a batch or in its last wave -- then
-       started below window 30, skipped s' digits 7 / 15 and rejected a valid signature with ERR_MSG:
-       tests/test_gpu_hs_top.py, tests/golden/hs_top.npz.) */
-    int wb = i < 8 ? 4*i : 4*(i-8) + 2;
-    top = ( db && wb > top ) ? wb : top;
-  }
+  /* the walks add s' digit i at window 4i (i < 8) or 4(i-8)+2 (i >= 8, the 2^120 B table): the top
+     window counts these too.  (Round 4 took it from c0 / c1 alone; a wave whose pending signatures all
+     had c0, c1 < 2^120 -- ~7.5e-6 of hash-distributed k, alone in a batch or in its last wave -- then
+     started below window 30, skipped s' digits 7 / 15 and rejected a valid signature with ERR_MSG:
+     tests/test_gpu_hs_top.py, tests/golden/hs_top.npz.) */
+  top = store_digits_B( sp, s, n, digB, top, []( int i ) { return i < 8 ? 4*i : 4*(i-8) + 2; } );
   htop[s] = (unsigned char)top;                     /* highest window with a nonzero digit of c0, c1 or s' */
 }
 
@@ -496,6 +497,7 @@ FD_DEV void hs_store_digits_hot( u32 const c0[ 7 ], u32 const c1m[ 5 ], int c1ne
     digR[(size_t)i*n + col] = (i8)( c1neg ? -dr : dr );
     top = ( dr && i > top ) ? i : top;
   }
+  /* (store_digits_B's loop, written out: through the shared copy fd_hashh_kernel<1> compiles differently) */
   int carry = 0;
 #pragma unroll
   for( int i=0; i<FD_BDIG; i++ ) {
@@ -549,15 +551,31 @@ FD_DEV int result_code( int code, u32 pa, u32 pr, int semantics, int defer ) {
    the decodes; writes ERR_SIG (malformed or S >= l) or SUCCESS and
    hashes every well-formed signature; fd_table_kernel applies the
    point statuses. */
+/* The front of every hash role (hash_one, hashh_one, hashh_one_q): signature s's transaction descriptor d and
+   its signer j; 0 if the descriptor is malformed.  (Only this much is shared: with S's load and check in
+   here too, every hash kernel compiles differently.) */
+FD_DEV int sig_desc( fdgpu_txn_desc_t const * __restrict__ desc, u32 const * __restrict__ map, u32 s,
+                     fdgpu_txn_desc_t & d, u32 & j ) {
+  u32 m = map[s];
+  u32 t = m & 0xffffffu;
+  j = m >> 24;
+  d = desc[t];
+  return txn_desc_ok( d );
+}
+
+/* h = signature s's SHA-512(R||A||M), computed beforehand (messages beyond the descriptor range, verify_long) */
+FD_DEV void khash_load( u32 h[ 16 ], uint4 const * __restrict__ khash, u32 s ) {
+#pragma unroll
+  for( int i=0; i<4; i++ ) { uint4 v = khash[4*(size_t)s + i]; h[4*i] = v.x; h[4*i+1] = v.y; h[4*i+2] = v.z; h[4*i+3] = v.w; }
+}
+
 FD_DEV void hash_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
                       u32 const * __restrict__ map, u32 s, size_t n, int semantics, int defer,
                       unsigned char const * __restrict__ pstat, i8 * __restrict__ code_out,
                       i8 * __restrict__ digA, short * __restrict__ digB, uint4 * __restrict__ Rraw,
                       uint4 const * __restrict__ khash ) {
-  u32 m = map[s];
-  u32 t = m & 0xffffffu, j = m >> 24;
-  fdgpu_txn_desc_t d = desc[t];
-  if( !txn_desc_ok( d ) ) { code_out[s] = FD_ED25519_ERR_SIG; return; }
+  fdgpu_txn_desc_t d; u32 j;
+  if( !sig_desc( desc, map, s, d, j ) ) { code_out[s] = FD_ED25519_ERR_SIG; return; }
   unsigned char const * base = payload + d.payload_off;
   u32 Sw[8];
   fd_load_words<8>( Sw, base + d.signature_off + 64u*j + 32u );
@@ -575,10 +593,8 @@ FD_DEV void hash_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc
   }
   fd_load_words<8>( Aw, base + d.acct_addr_off + 32u*j );
   u32 h[16], k[8];
-  if( khash ) {                                  /* digest computed beforehand (messages beyond the descriptor range) */
-#pragma unroll
-    for( int i=0; i<4; i++ ) { uint4 v = khash[4*(size_t)s + i]; h[4*i] = v.x; h[4*i+1] = v.y; h[4*i+2] = v.z; h[4*i+3] = v.w; }
-  } else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
+  if( khash ) khash_load( h, khash, s );
+  else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
   sc_reduce( k, h );
   store_digits( k, Sw, s, n, digA, digB );
 }
@@ -627,10 +643,8 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
                        unsigned char * __restrict__ htop, u32 const * __restrict__ arep = (u32 const *)0,
                        unsigned char const * __restrict__ astat = (unsigned char const *)0, u32 kcol = 0u, int hot = 0 ) {
   u32 col = KS ? kcol : s;
-  u32 m = map[s];
-  u32 t = m & 0xffffffu, j = m >> 24;
-  fdgpu_txn_desc_t d = desc[t];
-  if( !txn_desc_ok( d ) ) { code_out[s] = FD_ED25519_ERR_SIG; return; }
+  fdgpu_txn_desc_t d; u32 j;
+  if( !sig_desc( desc, map, s, d, j ) ) { code_out[s] = FD_ED25519_ERR_SIG; return; }
   unsigned char const * base = payload + d.payload_off;
   u32 Sw[8];
   fd_load_words<8>( Sw, base + d.signature_off + 64u*j + 32u );
@@ -644,10 +658,8 @@ FD_DEV void hashh_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
   fd_load_words<8>( Rw, base + d.signature_off + 64u*j );
   fd_load_words<8>( Aw, base + d.acct_addr_off + 32u*j );
   u32 h[16], k[8];
-  if( khash ) {
-#pragma unroll
-    for( int i=0; i<4; i++ ) { uint4 v = khash[4*(size_t)s + i]; h[4*i] = v.x; h[4*i+1] = v.y; h[4*i+2] = v.z; h[4*i+3] = v.w; }
-  } else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
+  if( khash ) khash_load( h, khash, s );
+  else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
   sc_reduce( k, h );
   u32 c0[5], c1m[5], sp[8]; int c1neg = 0;
   if( KS && hot ) {
@@ -676,10 +688,8 @@ FD_DEV void hashh_one_q( unsigned char const * __restrict__ payload, fdgpu_txn_d
                          i8 * __restrict__ digA, i8 * __restrict__ digR, short * __restrict__ digB,
                          u32 * __restrict__ slow, u32 * __restrict__ slow_cnt, uint4 const * __restrict__ khash,
                          u32 force_slow, unsigned char * __restrict__ htop, u32 q, u32 qbase ) {
-  u32 m = map[s];
-  u32 t = m & 0xffffffu, j = m >> 24;
-  fdgpu_txn_desc_t d = desc[t];
-  if( !txn_desc_ok( d ) ) { if( !q ) code_out[s] = FD_ED25519_ERR_SIG; return; }
+  fdgpu_txn_desc_t d; u32 j;
+  if( !sig_desc( desc, map, s, d, j ) ) { if( !q ) code_out[s] = FD_ED25519_ERR_SIG; return; }
   unsigned char const * base = payload + d.payload_off;
   u32 Sw[8];
   fd_load_words<8>( Sw, base + d.signature_off + 64u*j + 32u );
@@ -690,8 +700,7 @@ FD_DEV void hashh_one_q( unsigned char const * __restrict__ payload, fdgpu_txn_d
   u32 h[16], k[8];
   if( khash ) {                                  /* digests computed before (long messages): lane 0 reads its own */
     if( q ) return;
-#pragma unroll
-    for( int i=0; i<4; i++ ) { uint4 v = khash[4*(size_t)s + i]; h[4*i] = v.x; h[4*i+1] = v.y; h[4*i+2] = v.z; h[4*i+3] = v.w; }
+    khash_load( h, khash, s );
   } else {
     fd_sha512_RAM_quad( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off, q, qbase );
     if( q ) return;
@@ -1361,6 +1370,10 @@ FD_DEV void pair_add( fe & E, fe & F, fe & G, fe & H, int h, fe const & m0, fe c
    entry per even window ([0..32768]B / 2^120 B), Q == O at the end.
    Signatures on the slow list (FD_PEND_SLOW) are left to slowl_tail (run by fd_dsm2_kernel<.,1> after
    the walk). */
+/* c = neg ? -c : c: the coordinate 2dT of a negated table entry, in the many-lane walks.  (fd_dsm4_walk
+   writes it out: through this function both fd_dsm4_kernel instances compile differently.) */
+FD_DEV void fe_cneg( fe & c, int neg ) { fe nc; fe_neg( nc, c ); fe_sel( c, neg, nc, c ); }
+
 template<int FM, int HS>
 FD_DEV void
 fd_dsm2_walk( u32                      nsig,
@@ -1428,13 +1441,13 @@ fd_dsm2_walk( u32                      nsig,
     }
     fe_from_quads( q0, araw[0], araw[1] );
     fe_from_quads( q1, araw[2], araw[3] );
-    { fe nq; fe_neg( nq, q1 ); fe_sel( q1, !h && da < 0, nq, q1 ); }
+    fe_cneg( q1, !h && da < 0 );
     pair_add<FM>( E, F, G, H, h, m0, m1, q0, q1 );
     pair_mstep<FM>( m0, m1, h, E, F, G, H );
     if( HS ) {
       fe_from_quads( q0, rraw[0], rraw[1] );
       fe_from_quads( q1, rraw[2], rraw[3] );
-      { fe nq; fe_neg( nq, q1 ); fe_sel( q1, !h && dr < 0, nq, q1 ); }
+      fe_cneg( q1, !h && dr < 0 );
       pair_add<FM>( E, F, G, H, h, m0, m1, q0, q1 );
       pair_mstep<FM>( m0, m1, h, E, F, G, H );
     }
@@ -1443,7 +1456,7 @@ fd_dsm2_walk( u32                      nsig,
       if( h ) q1 = one;
       else {
         fe_from_quads( q1, braw[2], braw[3] );
-        fe nq; fe_neg( nq, q1 ); fe_sel( q1, db < 0, nq, q1 );
+        fe_cneg( q1, db < 0 );
       }
       pair_add<FM>( E, F, G, H, h, m0, m1, q0, q1 );
       pair_mstep<FM>( m0, m1, h, E, F, G, H );
@@ -1679,17 +1692,7 @@ fd_dsm4_kernel( u32                      nsig,
    form (Y+X, Y-X, 2dT, Z; one multiplication), is added to quad 0's, and
    the sum is tested for the identity.  Every lane of a group leaves
    together (result codes first, like fd_dsm4_kernel<.,1>). */
-FD_DEV void fe_from_upper_quad( fe & r, fe const & a ) {   /* lanes 0-3 of a group of 8 read lanes 4-7 */
-  asm volatile( "s_nop 1\n\t"
-                FD_DPP_MOV( 0, 10, "row_shl:4" ) FD_DPP_MOV( 1, 11, "row_shl:4" ) FD_DPP_MOV( 2, 12, "row_shl:4" )
-                FD_DPP_MOV( 3, 13, "row_shl:4" ) FD_DPP_MOV( 4, 14, "row_shl:4" ) FD_DPP_MOV( 5, 15, "row_shl:4" )
-                FD_DPP_MOV( 6, 16, "row_shl:4" ) FD_DPP_MOV( 7, 17, "row_shl:4" ) FD_DPP_MOV( 8, 18, "row_shl:4" )
-                FD_DPP_MOV( 9, 19, "row_shl:4" )
-                : "=&v"( r.v[0] ), "=&v"( r.v[1] ), "=&v"( r.v[2] ), "=&v"( r.v[3] ), "=&v"( r.v[4] ),
-                  "=&v"( r.v[5] ), "=&v"( r.v[6] ), "=&v"( r.v[7] ), "=&v"( r.v[8] ), "=&v"( r.v[9] )
-                : "v"( a.v[0] ), "v"( a.v[1] ), "v"( a.v[2] ), "v"( a.v[3] ), "v"( a.v[4] ),
-                  "v"( a.v[5] ), "v"( a.v[6] ), "v"( a.v[7] ), "v"( a.v[8] ), "v"( a.v[9] ) );
-}
+FD_DEF_FE_DPP( fe_from_upper_quad, "row_shl:4" )   /* lanes 0-3 of a group of 8 read lanes 4-7 */
 
 template<int FM>
 FD_DEV void
@@ -1742,14 +1745,14 @@ fd_dsm8_walk( u32                      nsig,
       for( int r=0; r<4; r++ ) { quad_dbl<FM>( E, F, G, H, q, m ); quad_mstep<FM>( m, q, E, F, G, H ); }
     }
     fe_from_quads( cc, araw[0], araw[1] );
-    { fe nc; fe_neg( nc, cc ); fe_sel( cc, q==2 && da < 0, nc, cc ); }
+    fe_cneg( cc, q==2 && da < 0 );
     quad_add<FM>( E, F, G, H, q, m, cc );
     quad_mstep<FM>( m, q, E, F, G, H );
     if( bw ) {
       if( q == 3 ) cc = one;
       else {
         fe_from_quads( cc, braw[0], braw[1] );
-        fe nc; fe_neg( nc, cc ); fe_sel( cc, q==2 && db < 0, nc, cc );
+        fe_cneg( cc, q==2 && db < 0 );
       }
       quad_add<FM>( E, F, G, H, q, m, cc );
       quad_mstep<FM>( m, q, E, F, G, H );
@@ -2535,8 +2538,14 @@ struct fd_slot {               /* one in-flight host batch of the async pipeline
   int                path;     /* the engine path its batch ran (FDGPU_PATH_* or lanes, fdgpu_ed25519_front_batch) */
 };
 
+#define FD_NSLOT 4     /* pinned staging slots of the async pipeline */
+#define FD_NRING 64    /* batches whose kernel boundaries are kept while timing is on */
+#define FD_NGT   64    /* gathers timed at once */
+
 struct fdgpu_ed25519_ctx {
   int device, semantics, timing;
+  std::vector<void *> dev_mem, pin_mem;   /* every device / pinned buffer of the context and its slots (ctx_dev_alloc,
+                                             ctx_pin_alloc): what fdgpu_ed25519_ctx_delete frees */
   unsigned long max_txn, max_sig, max_payload;
   hipStream_t stream;
   hipStream_t cstream;           /* copy stream of large host batches (verify_host_pipelined) */
@@ -2599,13 +2608,11 @@ struct fdgpu_ed25519_ctx {
   uint4 * d_htab;                /*   [hot_cap][2][8][8] the high tables, 2 KB per hot key */
   uint4 * d_btabh;               /*   [3][FD_BTAB_ENTRIES][6] [0..32768](2^e B), e = 72, 140, 196 */
   hipEvent_t ev[5];
-  enum { NRING = 64 };
-  hipEvent_t ring[ NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
+  hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
   unsigned long ring_cnt;
-  /* async pipeline: NSLOT pinned staging slots, all on ctx->stream */
-  enum { NSLOT = 4 };
-  fd_slot slot[ NSLOT ];
+  /* async pipeline: FD_NSLOT pinned staging slots, all on ctx->stream */
+  fd_slot slot[ FD_NSLOT ];
   int cur;                       /* slot being filled */
   int fault;                     /* a batch failed on the device: the pipeline refuses new work */
   int dbg_fail_issue;            /* test hook (fdgpu_ed25519_debug_fail_launch): the launch thread fails batch launches */
@@ -2619,10 +2626,9 @@ struct fdgpu_ed25519_ctx {
   unsigned long * d_gcnt;        /*   gather blocks completed (device counter) */
   unsigned long   g_launched;    /*   records whose gather has been launched, cumulative */
   unsigned        gather_cus;    /*   CUs reserved for the gathers (fdgpu_ed25519_reserve_gather_cus), 0 = none */
-  enum { NGT = 64 };
-  unsigned long * h_gtime;       /*   pinned [NGT][2]: GPU clock (100 MHz ticks) at a gather's start / end */
+  unsigned long * h_gtime;       /*   pinned [FD_NGT][2]: GPU clock (100 MHz ticks) at a gather's start / end */
   unsigned long * d_gtime;
-  struct { unsigned long target, t_launch, t_issue; } gt[ NGT ];   /* host side of those gathers: count they end at,
+  struct { unsigned long target, t_launch, t_issue; } gt[ FD_NGT ];   /* host side of those gathers: count they end at,
                                                                        queued ns, issued ns (the runtime call) */
   unsigned long   gt_head, gt_tail;
   double          gclk_off_ns;   /*   GPU clock ns - host CLOCK_MONOTONIC ns (calibrated once) */
@@ -2630,15 +2636,15 @@ struct fdgpu_ed25519_ctx {
   unsigned long   gs_n, gs_start_sum, gs_start_max, gs_run_sum, gs_run_max;   /* fdgpu_ed25519_gather_stats */
   unsigned long   gs_issue_sum, gs_issue_max, gs_issue_slow;
   long            last_gt;       /*   gt[] entry of the last gather launched (-1: untimed) */
-  unsigned long * h_stamp;       /*   pinned [NSLOT][2] + 1: per slot the GPU clock when its verify kernels start
-                                      (fd_stamp_kernel) and end (fd_done_kernel); [2 NSLOT]: clock calibration */
+  unsigned long * h_stamp;       /*   pinned [FD_NSLOT][2] + 1: per slot the GPU clock when its verify kernels start
+                                      (fd_stamp_kernel) and end (fd_done_kernel); [2 FD_NSLOT]: clock calibration */
   unsigned long * d_stamp;
   unsigned long   ph[ 9 ];       /*   fdgpu_ed25519_phase_stats */
   unsigned long n_batches, n_txns;                /* async batches launched, transactions in them */
   unsigned long launch_ns;                        /* host time inside slot_launch */
   unsigned long volatile * h_flag;                /* per slot: completion token written by fd_done_kernel (pinned);
-                                                     [NSLOT]: the synchronous calls' (stream_wait);
-                                                     [NSLOT+1]: records gathered, cumulative (fd_gather_kernel) */
+                                                     [FD_NSLOT]: the synchronous calls' (stream_wait);
+                                                     [FD_NSLOT+1]: records gathered, cumulative (fd_gather_kernel) */
   unsigned long sync_token;
   unsigned long * d_flag;
   unsigned long lat_hist[ FDGPU_LAT_BUCKETS ];    /* launch -> verdicts seen by poll, quarter-octave buckets */
@@ -2647,6 +2653,24 @@ struct fdgpu_ed25519_ctx {
                                                      else its launch thread does (fdgpu_ed25519_set_launcher) */
   char lerr[ 192 ];                               /* the launch thread's error, when it faulted the context */
 };
+
+/* Context memory: every device buffer of a context and of its slots comes from ctx_dev_alloc and every pinned
+   one from ctx_pin_alloc (which also gives its device view, if asked).  Both record the pointer, and
+   fdgpu_ed25519_ctx_delete frees from those records: a new buffer is named once, where it is allocated.
+   (d_khash lives inside verify_long only and is not recorded.) */
+template< class T > static hipError_t
+ctx_dev_alloc( fdgpu_ed25519_ctx_t * ctx, T ** p, size_t sz ) {
+  hipError_t e = hipMalloc( (void **)p, sz );
+  if( e == hipSuccess ) ctx->dev_mem.push_back( (void *)*p );
+  return e;
+}
+template< class T, class U = T > static hipError_t
+ctx_pin_alloc( fdgpu_ed25519_ctx_t * ctx, T ** p, size_t sz, U ** dev = NULL ) {
+  hipError_t e = hipHostMalloc( (void **)p, sz, hipHostMallocDefault );
+  if( e != hipSuccess ) return e;
+  ctx->pin_mem.push_back( (void *)*p );
+  return dev ? hipHostGetDevicePointer( (void **)dev, (void *)*p, 0 ) : hipSuccess;
+}
 
 /* Wait for everything queued on st in a synchronous host call.  A blocking
    hipStreamSynchronize sleeps and now and then wakes late (the host-staged
@@ -2661,11 +2685,11 @@ struct fdgpu_ed25519_ctx {
 static int stream_wait( fdgpu_ed25519_ctx_t * ctx, hipStream_t st, int pageable ) {
   if( !pageable ) {
     unsigned long tok = ++ctx->sync_token;
-    hipLaunchKernelGGL( fd_done_kernel, dim3(1), dim3(1), 0, st, ctx->d_flag + fdgpu_ed25519_ctx_t::NSLOT, tok, (unsigned long *)NULL );
+    hipLaunchKernelGGL( fd_done_kernel, dim3(1), dim3(1), 0, st, ctx->d_flag + FD_NSLOT, tok, (unsigned long *)NULL );
     if( hipGetLastError() == hipSuccess ) {
       unsigned long t0 = fd_now_ns();
       while( fd_now_ns() - t0 < FD_SYNC_SPIN_NS ) {
-        if( ctx->h_flag[ fdgpu_ed25519_ctx_t::NSLOT ] == tok ) {
+        if( ctx->h_flag[ FD_NSLOT ] == tok ) {
           /* the results the caller reads next were stored before the token (fd_done_kernel's release):
              keep those plain loads behind this volatile one */
           std::atomic_thread_fence( std::memory_order_acquire );
@@ -2758,7 +2782,7 @@ extern "C" char const * fdgpu_last_error( void ) { return fd_err.c_str(); }
    pipeline holds nothing */
 static int async_busy( fdgpu_ed25519_ctx_t const * ctx ) {
   if( !ctx->inflight.empty() ) return 1;
-  for( int i=0; i<fdgpu_ed25519_ctx_t::NSLOT; i++ ) if( ctx->slot[i].txn_cnt ) return 1;
+  for( int i=0; i<FD_NSLOT; i++ ) if( ctx->slot[i].txn_cnt ) return 1;
   return 0;
 }
 
@@ -2951,7 +2975,7 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
   if( !txn_cnt ) return 0;
   fd_batch b = { d_payload, d_desc, (u32)sig_cnt, (unsigned)( (sig_cnt + FD_WG - 1) / FD_WG ),
                  d_sig_out ? d_sig_out : ctx->d_code, st, ctx->ev };
-  if( ctx->timing ) { b.ev = ctx->ring[ ctx->ring_cnt % fdgpu_ed25519_ctx_t::NRING ]; ctx->ring_cnt++; }
+  if( ctx->timing ) { b.ev = ctx->ring[ ctx->ring_cnt % FD_NRING ]; ctx->ring_cnt++; }
   unsigned tg = (unsigned)( (txn_cnt + FD_WG - 1) / FD_WG );
   ctx->last_path = pick_path( ctx, b.nsig );
   if( b.nsig ) {
@@ -2969,9 +2993,6 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
   HIPCHK( hipGetLastError(), -3 );
   return 0;
 }
-
-extern "C" void fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx );
-static void launcher_drain( fdgpu_launcher_t * L );
 
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
@@ -2993,21 +3014,17 @@ slot_bufs( fdgpu_ed25519_ctx_t * ctx, int i ) {
   if( sl.h_payload ) return 0;
   unsigned long mp = ctx->max_payload, mt = ctx->max_txn;
   HIPCHK( hipSetDevice( ctx->device ), -1 );
-  HIPCHK( hipHostMalloc( (void**)&sl.h_payload, mp + FD_ARENA_SLACK, hipHostMallocDefault ), -1 );
-  HIPCHK( hipHostMalloc( (void**)&sl.h_desc, mt * sizeof(fdgpu_txn_desc_t), hipHostMallocDefault ), -1 );
-  HIPCHK( hipHostMalloc( (void**)&sl.h_txn_out, mt, hipHostMallocDefault ), -1 );
-  HIPCHK( hipHostMalloc( (void**)&sl.h_tags, mt * sizeof(unsigned long), hipHostMallocDefault ), -1 );
-  HIPCHK( hipMalloc( &sl.d_payload, mp + FD_ARENA_SLACK + FD_IMG_TAIL ), -1 );   /* + the last gathered record's image */
-  HIPCHK( hipMalloc( &sl.d_desc, mt * sizeof(fdgpu_txn_desc_t) ), -1 );
-  HIPCHK( hipMalloc( &sl.d_txn_out, mt ), -1 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl.hd_desc, (void *)sl.h_desc, 0 ), -1 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl.hd_txn_out, (void *)sl.h_txn_out, 0 ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl.h_payload, mp + FD_ARENA_SLACK ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl.h_desc, mt * sizeof(fdgpu_txn_desc_t), &sl.hd_desc ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl.h_txn_out, mt, &sl.hd_txn_out ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl.h_tags, mt * sizeof(unsigned long) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl.d_payload, mp + FD_ARENA_SLACK + FD_IMG_TAIL ), -1 );   /* + the last gathered record's image */
+  HIPCHK( ctx_dev_alloc( ctx, &sl.d_desc, mt * sizeof(fdgpu_txn_desc_t) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl.d_txn_out, mt ), -1 );
   memset( sl.h_payload, 0, FD_ARENA_SLACK );
   return 0;
 }
 
-/* allocations of a new context; on failure the caller deletes the
-   partially built context (every handle starts NULL) */
 __global__ void fd_clock_kernel( unsigned long * out ) {
   __hip_atomic_store( out, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
 }
@@ -3015,12 +3032,12 @@ __global__ void fd_clock_kernel( unsigned long * out ) {
 /* GPU clock -> host clock offset, from the shortest of three probe launches on the context's idle
    stream at creation (error <= half that round trip, ~10 us) */
 static void gclk_calibrate( fdgpu_ed25519_ctx_t * ctx ) {
-  unsigned long volatile * w = (unsigned long volatile *)( ctx->h_stamp + 2*fdgpu_ed25519_ctx_t::NSLOT );
+  unsigned long volatile * w = (unsigned long volatile *)( ctx->h_stamp + 2*FD_NSLOT );
   double best = 1e30;
   for( int k=0; k<3; k++ ) {
     w[0] = 0UL;
     unsigned long t0 = fd_now_ns();
-    hipLaunchKernelGGL( fd_clock_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_stamp + 2*fdgpu_ed25519_ctx_t::NSLOT );
+    hipLaunchKernelGGL( fd_clock_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_stamp + 2*FD_NSLOT );
     if( hipStreamSynchronize( ctx->stream ) != hipSuccess || !w[0] ) return;
     unsigned long t1 = fd_now_ns();
     if( (double)( t1 - t0 ) < best ) { best = (double)( t1 - t0 ); ctx->gclk_off_ns = (double)w[0] * 10.0 - 0.5 * ( (double)t0 + (double)t1 ); }
@@ -3028,6 +3045,8 @@ static void gclk_calibrate( fdgpu_ed25519_ctx_t * ctx ) {
   ctx->gclk_ok = 1;
 }
 
+/* allocations of a new context; on failure the caller deletes the
+   partially built context (every handle starts NULL) */
 static int
 ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned long max_sig,
           unsigned long max_payload_bytes, int semantics ) {
@@ -3036,30 +3055,30 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   size_t ns = max_sig;
   HIPCHK( hipStreamCreateWithFlags( &ctx->stream, hipStreamNonBlocking ), -1 );
 
-  HIPCHK( hipMalloc( &ctx->d_map,  ns * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_code, ns ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_pstat, 2*ns ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_tab,  ns * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_Rxy,  ns * 4 * sizeof(uint4) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_Axy,  ns * 4 * sizeof(uint4) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_digA, ns * 64 ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_digB, ns * FD_BDIG * sizeof(short) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_btab, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_rdesc, max_txn * sizeof(fdgpu_txn_desc_t) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_pflag, max_txn ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_P, ns * 30 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_O, ns * 10 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_blk, ( ( ns + FD_WG - 1 ) / FD_WG ) * 10 * sizeof(u32) ), -1 );
-  HIPCHK( hipMalloc( &ctx->d_slow, ( ns + FD_SW_CNT ) * sizeof(u32) ), -1 );   /* the list + the batch's counts (slow_word) */
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_map,  ns * sizeof(u32) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_code, ns ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_pstat, 2*ns ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_tab,  ns * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_Rxy,  ns * 4 * sizeof(uint4) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_Axy,  ns * 4 * sizeof(uint4) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_digA, ns * 64 ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_digB, ns * FD_BDIG * sizeof(short) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btab, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_rdesc, max_txn * sizeof(fdgpu_txn_desc_t) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_pflag, max_txn ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_P, ns * 30 * sizeof(u32) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_O, ns * 10 * sizeof(u32) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_blk, ( ( ns + FD_WG - 1 ) / FD_WG ) * 10 * sizeof(u32) ), -1 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_slow, ( ns + FD_SW_CNT ) * sizeof(u32) ), -1 );   /* the list + the batch's counts (slow_word) */
   HIPCHK( hipMemsetAsync( slow_word( ctx, 0 ), 0, FD_SW_CNT * sizeof(u32), ctx->stream ), -1 );
   fdgpu_debug_opts_t dbg; debug_opts_get( &dbg );   /* test / A/B choices (fdgpu_debug_set_opts), never the environment */
   ctx->half = dbg.half >= 0 ? dbg.half : FD_HALF;
   ctx->half_force_slow = dbg.half_force_slow;
   if( ctx->half ) {
-    HIPCHK( hipMalloc( &ctx->d_tabR, ns * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
-    HIPCHK( hipMalloc( &ctx->d_digR, ns * FD_HDIG ), -1 );
-    HIPCHK( hipMalloc( &ctx->d_htop, ns ), -1 );
-    HIPCHK( hipMalloc( &ctx->d_btab2, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_tabR, ns * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_digR, ns * FD_HDIG ), -1 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_htop, ns ), -1 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btab2, FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
     /* distinct keys decoded once (the decode lanes build the tables) */
     ctx->key_dedup = dbg.key_dedup != 1;
     if( ctx->key_dedup ) {
@@ -3067,22 +3086,22 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
       if( dbg.key_dedup != 2 ) while( slots < 2UL*ns && slots < ( 1UL << 31 ) ) slots <<= 1;
       ctx->kd_slots = (u32)slots; ctx->kd_tiny = dbg.key_dedup == 2; ctx->kd_probes = ctx->kd_tiny ? 2u : FD_KD_PROBES;
       ctx->kd_seed = 0u;
-      HIPCHK( hipMalloc( &ctx->d_ktab, slots * sizeof(u32) ), -1 );           /* (cleared per batch, launch_batch) */
-      HIPCHK( hipMalloc( &ctx->d_arep, ns * sizeof(u32) ), -1 );
-      HIPCHK( hipMalloc( &ctx->d_ulist, ns * sizeof(u32) ), -1 );
-      HIPCHK( hipMalloc( &ctx->d_astat, ns ), -1 );
+      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ktab, slots * sizeof(u32) ), -1 );           /* (cleared per batch, launch_batch) */
+      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_arep, ns * sizeof(u32) ), -1 );
+      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ulist, ns * sizeof(u32) ), -1 );
+      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_astat, ns ), -1 );
       /* the signatures of repeated keys walk 64 doublings (fd_keysplit_kernel) */
       ctx->key_split = dbg.key_split != 1;
       if( ctx->key_split ) {
         ctx->hot_min = dbg.key_split == 2 ? 2u : FD_HOT_MIN;
         ctx->hot_cap = (u32)( ns / ctx->hot_min );
         size_t hc = ctx->hot_cap ? ctx->hot_cap : 1UL;
-        HIPCHK( hipMalloc( &ctx->d_kcnt, ns * sizeof(u32) ), -1 );
-        HIPCHK( hipMalloc( &ctx->d_hidx, ns * sizeof(u32) ), -1 );
-        HIPCHK( hipMalloc( &ctx->d_hlist, hc * sizeof(u32) ), -1 );
-        HIPCHK( hipMalloc( &ctx->d_order, ns * sizeof(u32) ), -1 );
-        HIPCHK( hipMalloc( &ctx->d_htab, hc * 2 * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
-        HIPCHK( hipMalloc( &ctx->d_btabh, (size_t)3 * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_kcnt, ns * sizeof(u32) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_hidx, ns * sizeof(u32) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_hlist, hc * sizeof(u32) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_order, ns * sizeof(u32) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_htab, hc * 2 * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
+        HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabh, (size_t)3 * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
       }
     }
   }
@@ -3095,7 +3114,7 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   ctx->gather_cu_spread = dbg.gather_cu_spread;
   ctx->quad_sha = dbg.quad_sha;
   for( int i=0; i<5; i++ ) HIPCHK( hipEventCreate( &ctx->ev[i] ), -1 );
-  for( int r=0; r<fdgpu_ed25519_ctx_t::NRING; r++ ) for( int i=0; i<5; i++ ) HIPCHK( hipEventCreate( &ctx->ring[r][i] ), -1 );
+  for( int r=0; r<FD_NRING; r++ ) for( int i=0; i<5; i++ ) HIPCHK( hipEventCreate( &ctx->ring[r][i] ), -1 );
   ctx->ring_cnt = 0;
   hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream, ctx->d_btab, 0 );
   if( ctx->half )
@@ -3107,15 +3126,13 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
                           ctx->d_btabh + (size_t)t * FD_BTAB_ENTRIES * 6, e[t] );
   }
   HIPCHK( hipGetLastError(), -1 );
-  for( int i=0; i<fdgpu_ed25519_ctx_t::NSLOT; i++ ) HIPCHK( hipEventCreateWithFlags( &ctx->slot[i].done, hipEventDisableTiming ), -1 );
-  HIPCHK( hipHostMalloc( (void **)&ctx->h_flag, ( fdgpu_ed25519_ctx_t::NSLOT + 2 ) * sizeof(unsigned long), hipHostMallocDefault ), -1 );
-  for( int i=0; i<=fdgpu_ed25519_ctx_t::NSLOT+1; i++ ) ctx->h_flag[i] = 0UL;   /* [NSLOT]: stream_wait's word, [NSLOT+1]: gathers */
-  HIPCHK( hipMalloc( &ctx->d_gcnt, sizeof(unsigned long) ), -1 );
+  for( int i=0; i<FD_NSLOT; i++ ) HIPCHK( hipEventCreateWithFlags( &ctx->slot[i].done, hipEventDisableTiming ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &ctx->h_flag, ( FD_NSLOT + 2 ) * sizeof(unsigned long), &ctx->d_flag ), -1 );
+  for( int i=0; i<=FD_NSLOT+1; i++ ) ctx->h_flag[i] = 0UL;   /* [FD_NSLOT]: stream_wait's word, [FD_NSLOT+1]: gathers */
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_gcnt, sizeof(unsigned long) ), -1 );
   HIPCHK( hipMemsetAsync( ctx->d_gcnt, 0, sizeof(unsigned long), ctx->stream ), -1 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&ctx->d_flag, (void *)ctx->h_flag, 0 ), -1 );
-  HIPCHK( hipHostMalloc( (void **)&ctx->h_stamp, ( 2*fdgpu_ed25519_ctx_t::NSLOT + 1 ) * sizeof(unsigned long), hipHostMallocDefault ), -1 );
-  memset( ctx->h_stamp, 0, ( 2*fdgpu_ed25519_ctx_t::NSLOT + 1 ) * sizeof(unsigned long) );
-  HIPCHK( hipHostGetDevicePointer( (void **)&ctx->d_stamp, (void *)ctx->h_stamp, 0 ), -1 );
+  HIPCHK( ctx_pin_alloc( ctx, &ctx->h_stamp, ( 2*FD_NSLOT + 1 ) * sizeof(unsigned long), &ctx->d_stamp ), -1 );
+  memset( ctx->h_stamp, 0, ( 2*FD_NSLOT + 1 ) * sizeof(unsigned long) );
   ctx->last_gt = -1;
   if( dbg.cu_exclusive > 0 && fdgpu_ed25519_set_cu_exclusive( ctx, dbg.cu_exclusive ) ) return -1;
   if( dbg.cu_exclusive < 0 ) ctx->excl_mode = -1;      /* explicitly off: a verify tile keeps it off too */
@@ -3128,78 +3145,15 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
   return 0;
 }
 
-extern "C" fdgpu_ed25519_ctx_t *
-fdgpu_ed25519_ctx_new( int device, unsigned long max_txn, unsigned long max_sig,
-                       unsigned long max_payload_bytes, int semantics ) {
-  if( max_txn==0 || max_txn >= (1UL<<24) || max_sig==0 || max_sig >= (1UL<<31) ) { fd_err = "bad sizes"; return NULL; }
-  if( semantics!=FDGPU_SEMANTICS_AVX512 && semantics!=FDGPU_SEMANTICS_REF ) { fd_err = "bad semantics"; return NULL; }
-  HIPCHK( hipSetDevice( device ), NULL );
-  fdgpu_ed25519_ctx_t * ctx = new fdgpu_ed25519_ctx_t();
-  if( ctx_init( ctx, device, max_txn, max_sig, max_payload_bytes, semantics ) ) {
-    std::string err = fd_err;
-    fdgpu_ed25519_ctx_delete( ctx );
-    fd_err = err;
-    return NULL;
-  }
-  return ctx;
-}
-
-extern "C" void
-fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx ) {
-  if( !ctx ) return;
-  (void)hipSetDevice( ctx->device );
-  if( ctx->launcher ) launcher_drain( ctx->launcher );   /* its queued calls are made before the streams drain */
-  /* every stream of the context drains before anything is freed: gathers of a slot that was still filling
-     (early copies, never launched) read its pinned descriptors and write its arena on the gather stream */
-  if( ctx->gstream ) (void)hipStreamSynchronize( ctx->gstream );
-  if( ctx->cstream ) (void)hipStreamSynchronize( ctx->cstream );
-  if( ctx->stream ) (void)hipStreamSynchronize( ctx->stream );
-  (void)hipFree( ctx->d_map ); (void)hipFree( ctx->d_code ); (void)hipFree( ctx->d_pstat ); (void)hipFree( ctx->d_tab );
-  (void)hipFree( ctx->d_Rxy ); (void)hipFree( ctx->d_Axy ); (void)hipFree( ctx->d_digA ); (void)hipFree( ctx->d_digB );
-  (void)hipFree( ctx->d_btab ); (void)hipFree( ctx->d_rdesc ); (void)hipFree( ctx->d_pflag );
-  (void)hipFree( ctx->d_tabR ); (void)hipFree( ctx->d_digR ); (void)hipFree( ctx->d_htop ); (void)hipFree( ctx->d_btab2 );
-  (void)hipFree( ctx->d_ktab ); (void)hipFree( ctx->d_arep ); (void)hipFree( ctx->d_ulist ); (void)hipFree( ctx->d_astat );
-  (void)hipFree( ctx->d_kcnt ); (void)hipFree( ctx->d_hidx ); (void)hipFree( ctx->d_hlist ); (void)hipFree( ctx->d_order );
-  (void)hipFree( ctx->d_htab ); (void)hipFree( ctx->d_btabh );
-  (void)hipFree( ctx->d_P ); (void)hipFree( ctx->d_O ); (void)hipFree( ctx->d_blk ); (void)hipFree( ctx->d_slow );
-  for( int i=0; i<5; i++ ) if( ctx->ev[i] ) (void)hipEventDestroy( ctx->ev[i] );
-  for( int r=0; r<fdgpu_ed25519_ctx_t::NRING; r++ ) for( int i=0; i<5; i++ ) if( ctx->ring[r][i] ) (void)hipEventDestroy( ctx->ring[r][i] );
-  for( int i=0; i<fdgpu_ed25519_ctx_t::NSLOT; i++ ) {
-    fd_slot & sl = ctx->slot[i];
-    if( sl.h_payload ) (void)hipHostFree( sl.h_payload );
-    if( sl.h_desc    ) (void)hipHostFree( sl.h_desc );
-    if( sl.h_txn_out ) (void)hipHostFree( sl.h_txn_out );
-    if( sl.h_tags    ) (void)hipHostFree( sl.h_tags );
-    if( sl.h_img     ) (void)hipHostFree( sl.h_img );
-    if( sl.h_fp      ) (void)hipHostFree( sl.h_fp );
-    if( sl.h_dtag    ) (void)hipHostFree( sl.h_dtag );
-    (void)hipFree( sl.d_dtag );
-    if( sl.h_gat     ) (void)hipHostFree( sl.h_gat );
-    (void)hipFree( sl.d_payload ); (void)hipFree( sl.d_desc ); (void)hipFree( sl.d_txn_out );
-    (void)hipFree( sl.d_img ); (void)hipFree( sl.d_fp ); (void)hipFree( sl.d_ovr );
-    if( sl.done ) (void)hipEventDestroy( sl.done );
-  }
-  if( ctx->cstream ) { (void)hipStreamSynchronize( ctx->cstream ); (void)hipStreamDestroy( ctx->cstream ); }
-  if( ctx->gstream ) { (void)hipStreamSynchronize( ctx->gstream ); (void)hipStreamDestroy( ctx->gstream ); }
-  if( ctx->gev ) (void)hipEventDestroy( ctx->gev );
-  if( ctx->h_gtime ) (void)hipHostFree( ctx->h_gtime );
-  (void)hipFree( ctx->d_gcnt );
-  if( ctx->h_flag ) (void)hipHostFree( (void *)ctx->h_flag );
-  if( ctx->h_stamp ) (void)hipHostFree( (void *)ctx->h_stamp );
-  for( unsigned long i=0; i<FD_PIPE_MAX; i++ ) if( ctx->pipe_ev[i] ) (void)hipEventDestroy( ctx->pipe_ev[i] );
-  if( ctx->stream ) (void)hipStreamDestroy( ctx->stream );
-  delete ctx;
-}
-
 extern "C" void fdgpu_ed25519_set_timing( fdgpu_ed25519_ctx_t * ctx, int enable ) { ctx->timing = enable; ctx->ring_cnt = 0; }
 
 /* mean duration of kernel idx over the batches launched since timing was
-   enabled (at most the last NRING), from HIP events recorded on the
+   enabled (at most the last FD_NRING), from HIP events recorded on the
    stream the kernels ran on */
 extern "C" float
 fdgpu_ed25519_kernel_ms( fdgpu_ed25519_ctx_t * ctx, int idx ) {
   if( idx<0 || idx>4 || !ctx->ring_cnt ) return -1.f;
-  unsigned long n = ctx->ring_cnt < (unsigned long)fdgpu_ed25519_ctx_t::NRING ? ctx->ring_cnt : (unsigned long)fdgpu_ed25519_ctx_t::NRING;
+  unsigned long n = ctx->ring_cnt < (unsigned long)FD_NRING ? ctx->ring_cnt : (unsigned long)FD_NRING;
   /* 0 prep, 1 walk, 2 reduce; throughput path's prep split: 3 the decode kernel, 4 the hash (+ table) kernels */
   static int const from[5] = { 0, 1, 2, 0, 4 }, to[5] = { 1, 2, 3, 4, 1 };
   double sum = 0.;
@@ -3263,7 +3217,39 @@ fdgpu_ed25519_verify_txns_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const
                        stream ? (hipStream_t)stream : ctx->stream );
 }
 
-static unsigned char * region_dev( void const * p, unsigned long sz );
+/* Host regions the GPU may read or write directly (fdgpu_host_alloc
+   allocations and fdgpu_host_register-ed ranges): host base -> device
+   address, for the gather path and for payloads the host calls read in place. */
+/* A fixed table read without a lock (every tile thread looks its frags up
+   here in during_frag; a global mutex there was contended by all of them):
+   writers (register / unregister, rare) serialise on a mutex, fill an
+   entry's fields and then publish it with a release store of its size; a
+   removed entry's size drops to 0 first. */
+#define FD_REGION_MAX 256
+struct fd_region { unsigned char const * h; unsigned char * d; std::atomic<unsigned long> sz; int refs, shared; };
+static std::mutex g_reg_mu;
+static fd_region g_regions[ FD_REGION_MAX ];
+static std::atomic<int> g_region_cnt{ 0 };
+
+/* device address of [p, p+sz) if it lies inside one registered region, else NULL */
+static unsigned char * region_dev( void const * p, unsigned long sz ) {
+  unsigned char const * q = (unsigned char const *)p;
+  /* a tile's frags come from one region: try the thread's last hit first (re-validated like
+     any entry, so a removed or reused entry is never trusted) */
+  static thread_local int hint = 0;
+  int n = g_region_cnt.load( std::memory_order_acquire );
+  if( hint < n ) {
+    unsigned long rs = g_regions[hint].sz.load( std::memory_order_acquire );
+    unsigned char const * h = g_regions[hint].h;
+    if( rs && q >= h && q + sz <= h + rs ) return g_regions[hint].d + ( q - h );
+  }
+  for( int i=0; i<n; i++ ) {
+    unsigned long rs = g_regions[i].sz.load( std::memory_order_acquire );
+    unsigned char const * h = g_regions[i].h;
+    if( rs && q >= h && q + sz <= h + rs ) { hint = i; return g_regions[i].d + ( q - h ); }
+  }
+  return NULL;
+}
 
 /* Host-side validation of a batch before staging: payload bounds and
    the sig_base prefix (the device kernels additionally bound-check every
@@ -3277,6 +3263,32 @@ static int check_batch( fdgpu_txn_desc_t const * desc, unsigned long txn_cnt, un
     s += desc[i].sig_cnt;
   }
   *sig_total = s;
+  return 0;
+}
+
+/* What the synchronous host calls share.  sync_ctx: is there a context (and, for the calls that pack
+   records into it, a staging slot)?  sync_begin, once the call's own arguments are checked: the calls
+   stage through slot 0, so only while the async pipeline holds nothing.  sync_finish: slot 0's
+   transaction codes (and the signature codes, if asked for) back to the caller, behind everything queued
+   on the context's stream; pageable = 1 if the call queued a copy into pageable host memory (stream_wait). */
+static int sync_ctx( fdgpu_ed25519_ctx_t const * ctx, int staged ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( staged && !ctx->slot[0].h_payload ) { fd_err = "ctx has no staging buffers (max_payload_bytes==0)"; return -3; }
+  return 0;
+}
+static int sync_begin( fdgpu_ed25519_ctx_t * ctx ) {
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  if( async_busy( ctx ) ) { fd_err = "async batches pending or in flight"; return -1; }
+  return 0;
+}
+static int sync_finish( fdgpu_ed25519_ctx_t * ctx, unsigned long txn_cnt, signed char * txn_out,
+                        signed char * sig_out, unsigned long nsig, int pageable ) {
+  fd_slot & sl = ctx->slot[0];
+  hipStream_t st = ctx->stream;
+  HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, txn_cnt, hipMemcpyDeviceToHost, st ), -2 );
+  if( sig_out && nsig ) HIPCHK( hipMemcpyAsync( sig_out, ctx->d_code, nsig, hipMemcpyDeviceToHost, st ), -2 );
+  if( stream_wait( ctx, st, pageable || ( sig_out && nsig ) ) ) return -2;
+  memcpy( txn_out, sl.h_txn_out, txn_cnt );
   return 0;
 }
 
@@ -3332,25 +3344,21 @@ verify_host_pipelined( fdgpu_ed25519_ctx_t * ctx, unsigned char const * payload,
                            sl.d_txn_out + txn_lo[i], ctx->d_code + sig_lo[i], st );
     if( rc ) return rc;
   }
-  HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, txn_cnt, hipMemcpyDeviceToHost, st ), -2 );
-  if( sig_out && nsig ) HIPCHK( hipMemcpyAsync( sig_out, ctx->d_code, nsig, hipMemcpyDeviceToHost, st ), -2 );
-  if( stream_wait( ctx, st, sig_out && nsig ) ) return -2;
-  memcpy( txn_out, sl.h_txn_out, txn_cnt );
-  return 0;
+  return sync_finish( ctx, txn_cnt, txn_out, sig_out, nsig, 0 );
 }
 
 extern "C" int
 fdgpu_ed25519_verify_txns_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * payload, unsigned long payload_bytes,
                                 fdgpu_txn_desc_t const * desc, unsigned long txn_cnt,
                                 signed char * txn_out, signed char * sig_out ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  int rc = sync_ctx( ctx, 0 );
+  if( rc ) return rc;
   unsigned long nsig;
   if( check_batch( desc, txn_cnt, payload_bytes, &nsig ) ) return -1;
   if( txn_cnt > ctx->max_txn || nsig > ctx->max_sig || payload_bytes > ctx->max_payload ) { fd_err = "batch larger than ctx"; return -1; }
   if( !txn_cnt ) return 0;
-  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  if( ( rc = sync_begin( ctx ) ) ) return rc;
   fd_slot & sl = ctx->slot[0];
-  if( async_busy( ctx ) ) { fd_err = "async batches pending or in flight"; return -1; }
   hipStream_t st = ctx->stream;
   if( txn_cnt >= 2UL*FD_PIPE_SUB ) return verify_host_pipelined( ctx, payload, payload_bytes, desc, txn_cnt, nsig, txn_out, sig_out );
   memcpy( sl.h_desc, desc, txn_cnt * sizeof(fdgpu_txn_desc_t) );
@@ -3369,12 +3377,37 @@ fdgpu_ed25519_verify_txns_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
     HIPCHK( hipMemcpyAsync( sl.d_payload + off, sl.h_payload + off, end - off, hipMemcpyHostToDevice, st ), -2 );
   }
   }
-  int rc = launch_batch( ctx, sl.d_payload, sl.d_desc, txn_cnt, nsig, sl.d_txn_out, NULL, st );
-  if( rc ) return rc;
-  HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, txn_cnt, hipMemcpyDeviceToHost, st ), -2 );
-  if( sig_out && nsig ) HIPCHK( hipMemcpyAsync( sig_out, ctx->d_code, nsig, hipMemcpyDeviceToHost, st ), -2 );
-  if( stream_wait( ctx, st, sig_out && nsig ) ) return -2;
-  memcpy( txn_out, sl.h_txn_out, txn_cnt );
+  if( ( rc = launch_batch( ctx, sl.d_payload, sl.d_desc, txn_cnt, nsig, sl.d_txn_out, NULL, st ) ) ) return rc;
+  return sync_finish( ctx, txn_cnt, txn_out, sig_out, nsig, 0 );
+}
+
+/* Records scattered in host memory, verified through slot 0 in chunks of up to max_txn transactions /
+   max_sig signatures / max_payload bytes (the caller has checked that each record alone fits).
+   desc_of( i ) gives record i's descriptor -- its payload_off and sig_base are set here -- and
+   pack( i, dst ) writes its payload_sz bytes; out[i] gets its code. */
+template< class D, class P > static int
+verify_chunks( fdgpu_ed25519_ctx_t * ctx, unsigned long cnt, signed char * out, D desc_of, P pack ) {
+  fd_slot & sl = ctx->slot[0];
+  hipStream_t st = ctx->stream;
+  unsigned long done = 0;
+  while( done < cnt ) {
+    unsigned long n = 0, nsig = 0; size_t used = 0;
+    while( done + n < cnt && n < ctx->max_txn ) {
+      fdgpu_txn_desc_t d = desc_of( done + n );
+      if( used + d.payload_sz + 8UL > ctx->max_payload || nsig + d.sig_cnt > ctx->max_sig ) break;
+      pack( done + n, sl.h_payload + used );
+      d.payload_off = (unsigned)used; d.sig_base = (unsigned)nsig;
+      sl.h_desc[n] = d;
+      used = ( used + d.payload_sz + 7UL ) & ~(size_t)7; nsig += d.sig_cnt; n++;
+    }
+    memset( sl.h_payload + used, 0, FD_ARENA_SLACK );
+    HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, used + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
+    HIPCHK( hipMemcpyAsync( sl.d_desc, sl.h_desc, n * sizeof(fdgpu_txn_desc_t), hipMemcpyHostToDevice, st ), -2 );
+    int rc = launch_batch( ctx, sl.d_payload, sl.d_desc, n, nsig, sl.d_txn_out, NULL, st );
+    if( rc ) return rc;
+    if( ( rc = sync_finish( ctx, n, out + done, NULL, 0UL, 0 ) ) ) return rc;
+    done += n;
+  }
   return 0;
 }
 
@@ -3387,40 +3420,21 @@ extern "C" int
 fdgpu_ed25519_verify_many_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * const * msgs,
                                 unsigned long const * msg_szs, unsigned char const * const * sigs,
                                 unsigned char const * const * pubs, unsigned long cnt, signed char * out ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( !ctx->slot[0].h_payload ) { fd_err = "ctx has no staging buffers (max_payload_bytes==0)"; return -3; }
-  if( async_busy( ctx ) ) { fd_err = "async batches pending or in flight"; return -1; }
+  int rc = sync_ctx( ctx, 1 );
+  if( rc || ( rc = sync_begin( ctx ) ) ) return rc;
   for( unsigned long i=0; i<cnt; i++ )
     if( msg_szs[i] > 0xffffUL - 96UL || 96UL + msg_szs[i] + 8UL > ctx->max_payload ) { fd_err = "message too long"; return -1; }
-  HIPCHK( hipSetDevice( ctx->device ), -2 );
-  fd_slot & sl = ctx->slot[0];
-  hipStream_t st = ctx->stream;
-  unsigned long done = 0;
-  while( done < cnt ) {
-    unsigned long n = 0; size_t used = 0;
-    while( done + n < cnt && n < ctx->max_txn && n < ctx->max_sig ) {
-      unsigned long i = done + n;
-      size_t need = 96UL + msg_szs[i];
-      if( used + need + 8UL > ctx->max_payload ) break;
-      unsigned char * b = sl.h_payload + used;
+  return verify_chunks( ctx, cnt, out,
+    [&]( unsigned long i ) {
+      fdgpu_txn_desc_t d = {};
+      d.payload_sz = (unsigned short)( 96UL + msg_szs[i] );
+      d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
+      return d;
+    },
+    [&]( unsigned long i, unsigned char * b ) {
       memcpy( b, sigs[i], 64 ); memcpy( b + 64, pubs[i], 32 );
       if( msg_szs[i] ) memcpy( b + 96, msgs[i], msg_szs[i] );
-      fdgpu_txn_desc_t & d = sl.h_desc[n];
-      d.payload_off = (unsigned)used; d.sig_base = (unsigned)n; d.payload_sz = (unsigned short)need;
-      d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
-      used = ( used + need + 7UL ) & ~(size_t)7; n++;
-    }
-    memset( sl.h_payload + used, 0, FD_ARENA_SLACK );
-    HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, used + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
-    HIPCHK( hipMemcpyAsync( sl.d_desc, sl.h_desc, n * sizeof(fdgpu_txn_desc_t), hipMemcpyHostToDevice, st ), -2 );
-    int rc = launch_batch( ctx, sl.d_payload, sl.d_desc, n, n, sl.d_txn_out, NULL, st );
-    if( rc ) return rc;
-    HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, n, hipMemcpyDeviceToHost, st ), -2 );
-    if( stream_wait( ctx, st, 0 ) ) return -2;
-    memcpy( out + done, sl.h_txn_out, n );
-    done += n;
-  }
-  return 0;
+    } );
 }
 
 /* Transactions scattered in host memory, each already parsed (the replay
@@ -3434,38 +3448,15 @@ fdgpu_ed25519_verify_many_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
 extern "C" int
 fdgpu_ed25519_verify_txn_ptrs( fdgpu_ed25519_ctx_t * ctx, unsigned char const * const * payloads,
                                fdgpu_txn_desc_t const * desc, unsigned long cnt, signed char * out ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( !ctx->slot[0].h_payload ) { fd_err = "ctx has no staging buffers (max_payload_bytes==0)"; return -3; }
-  if( async_busy( ctx ) ) { fd_err = "async batches pending or in flight"; return -1; }
+  int rc = sync_ctx( ctx, 1 );
+  if( rc || ( rc = sync_begin( ctx ) ) ) return rc;
   for( unsigned long i=0; i<cnt; i++ )
     if( (unsigned long)desc[i].payload_sz + 8UL > ctx->max_payload || desc[i].sig_cnt > ctx->max_sig ) {
       fd_err = "transaction larger than the ctx"; return -1;
     }
-  HIPCHK( hipSetDevice( ctx->device ), -2 );
-  fd_slot & sl = ctx->slot[0];
-  hipStream_t st = ctx->stream;
-  unsigned long done = 0;
-  while( done < cnt ) {
-    unsigned long n = 0, nsig = 0; size_t used = 0;
-    while( done + n < cnt && n < ctx->max_txn ) {
-      fdgpu_txn_desc_t d = desc[ done + n ];
-      if( used + d.payload_sz + 8UL > ctx->max_payload || nsig + d.sig_cnt > ctx->max_sig ) break;
-      memcpy( sl.h_payload + used, payloads[ done + n ], d.payload_sz );
-      d.payload_off = (unsigned)used; d.sig_base = (unsigned)nsig;
-      sl.h_desc[n] = d;
-      used = ( used + d.payload_sz + 7UL ) & ~(size_t)7; nsig += d.sig_cnt; n++;
-    }
-    memset( sl.h_payload + used, 0, FD_ARENA_SLACK );
-    HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, used + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
-    HIPCHK( hipMemcpyAsync( sl.d_desc, sl.h_desc, n * sizeof(fdgpu_txn_desc_t), hipMemcpyHostToDevice, st ), -2 );
-    int rc = launch_batch( ctx, sl.d_payload, sl.d_desc, n, nsig, sl.d_txn_out, NULL, st );
-    if( rc ) return rc;
-    HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, n, hipMemcpyDeviceToHost, st ), -2 );
-    if( stream_wait( ctx, st, 0 ) ) return -2;
-    memcpy( out + done, sl.h_txn_out, n );
-    done += n;
-  }
-  return 0;
+  return verify_chunks( ctx, cnt, out,
+    [&]( unsigned long i ) { return desc[i]; },
+    [&]( unsigned long i, unsigned char * b ) { memcpy( b, payloads[i], desc[i].payload_sz ); } );
 }
 
 /* ---- batch SHA-512 ---------------------------------------------------- */
@@ -3559,15 +3550,20 @@ fdgpu_ed25519_verify_raw_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const 
                      stream ? (hipStream_t)stream : ctx->stream );
 }
 
-/* host side of the raw path: signature lanes from each payload's first
-   byte (the parsed signature_cnt, fd_txn_parse.c:86) and their prefix */
+/* signature lanes of a raw payload: its first byte (the parsed signature_cnt, fd_txn_parse.c:86),
+   0 where that cannot be a count */
+static inline unsigned raw_lanes( unsigned char const * payload, unsigned long payload_sz ) {
+  unsigned b0 = payload_sz ? payload[0] : 0u;
+  return ( b0 >= 1u && b0 <= 16u ) ? b0 : 0u;
+}
+
+/* host side of the raw path: each payload's signature lanes and their prefix */
 static int stage_raw( unsigned char const * payload, unsigned long payload_bytes, fdgpu_txn_raw_t * raw,
                       unsigned long txn_cnt, unsigned long * sig_total ) {
   unsigned long s = 0;
   for( unsigned long i=0; i<txn_cnt; i++ ) {
     if( (unsigned long)raw[i].payload_off + raw[i].payload_sz > payload_bytes ) { fd_err = "payload out of arena"; return -1; }
-    unsigned b0 = raw[i].payload_sz ? payload[ raw[i].payload_off ] : 0u;
-    raw[i].sig_lanes = (unsigned char)( ( b0 >= 1u && b0 <= 16u ) ? b0 : 0u );
+    raw[i].sig_lanes = (unsigned char)raw_lanes( payload + raw[i].payload_off, raw[i].payload_sz );
     raw[i].sig_base  = (unsigned)s;
     s += raw[i].sig_lanes;
   }
@@ -3579,15 +3575,15 @@ extern "C" int
 fdgpu_ed25519_verify_raw_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * payload, unsigned long payload_bytes,
                                fdgpu_txn_raw_t * raw, unsigned long txn_cnt, signed char * txn_out,
                                unsigned char * img, unsigned long img_stride, unsigned short * fp ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  int rc = sync_ctx( ctx, 0 );
+  if( rc ) return rc;
   unsigned long nsig;
   if( stage_raw( payload, payload_bytes, raw, txn_cnt, &nsig ) ) return -1;
   if( txn_cnt > ctx->max_txn || nsig > ctx->max_sig || payload_bytes > ctx->max_payload ) { fd_err = "batch larger than ctx"; return -1; }
   if( img && img_stride < 852UL ) { fd_err = "img_stride < FD_TXN_MAX_SZ"; return -1; }
   if( !txn_cnt ) return 0;
-  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  if( ( rc = sync_begin( ctx ) ) ) return rc;
   fd_slot & sl = ctx->slot[0];
-  if( async_busy( ctx ) ) { fd_err = "async batches pending or in flight"; return -1; }
   memcpy( sl.h_payload, payload, payload_bytes );
   memset( sl.h_payload + payload_bytes, 0, FD_ARENA_SLACK );
   memcpy( sl.h_desc, raw, txn_cnt * sizeof(fdgpu_txn_raw_t) );
@@ -3597,15 +3593,11 @@ fdgpu_ed25519_verify_raw_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * 
   if( fp  ) HIPCHK( hipMallocAsync( (void **)&d_fp,  txn_cnt * sizeof(unsigned short), st ), -2 );
   HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, payload_bytes + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
   HIPCHK( hipMemcpyAsync( sl.d_desc, sl.h_desc, txn_cnt * sizeof(fdgpu_txn_raw_t), hipMemcpyHostToDevice, st ), -2 );
-  int rc = launch_raw( ctx, sl.d_payload, (fdgpu_txn_raw_t const *)sl.d_desc, txn_cnt, nsig, sl.d_txn_out, d_img,
-                       img_stride, d_fp, st );
-  if( rc ) return rc;
-  HIPCHK( hipMemcpyAsync( sl.h_txn_out, sl.d_txn_out, txn_cnt, hipMemcpyDeviceToHost, st ), -2 );
+  if( ( rc = launch_raw( ctx, sl.d_payload, (fdgpu_txn_raw_t const *)sl.d_desc, txn_cnt, nsig, sl.d_txn_out, d_img,
+                         img_stride, d_fp, st ) ) ) return rc;
   if( img ) { HIPCHK( hipMemcpyAsync( img, d_img, txn_cnt * img_stride, hipMemcpyDeviceToHost, st ), -2 ); HIPCHK( hipFreeAsync( d_img, st ), -2 ); }
   if( fp  ) { HIPCHK( hipMemcpyAsync( fp, d_fp, txn_cnt * sizeof(unsigned short), hipMemcpyDeviceToHost, st ), -2 ); HIPCHK( hipFreeAsync( d_fp, st ), -2 ); }
-  if( stream_wait( ctx, st, img || fp ) ) return -2;
-  memcpy( txn_out, sl.h_txn_out, txn_cnt );
-  return 0;
+  return sync_finish( ctx, txn_cnt, txn_out, NULL, 0UL, img || fp );
 }
 
 /* ---- async submit / poll ------------------------------------------ */
@@ -3627,8 +3619,8 @@ static std::atomic<unsigned long> g_pause_n{ 0 };
 
 /* account the timed gathers whose count has been reached */
 static void gather_times( fdgpu_ed25519_ctx_t * ctx, unsigned long gathered ) {
-  while( ctx->gt_head < ctx->gt_tail && ctx->gt[ ctx->gt_head % fdgpu_ed25519_ctx_t::NGT ].target <= gathered ) {
-    unsigned long i = ctx->gt_head % fdgpu_ed25519_ctx_t::NGT;
+  while( ctx->gt_head < ctx->gt_tail && ctx->gt[ ctx->gt_head % FD_NGT ].target <= gathered ) {
+    unsigned long i = ctx->gt_head % FD_NGT;
     unsigned long const volatile * w = (unsigned long const volatile *)( ctx->h_gtime + 2*i );
     if( ctx->gclk_ok && w[0] && w[1] >= w[0] ) {
       double st = (double)w[0] * 10.0 - ctx->gclk_off_ns - (double)ctx->gt[i].t_launch;
@@ -3653,10 +3645,8 @@ static void gather_times( fdgpu_ed25519_ctx_t * ctx, unsigned long gathered ) {
 
 /* the gather stream and its timing ring (on first use, or by fdgpu_ed25519_prepare) */
 static int gather_init( fdgpu_ed25519_ctx_t * ctx ) {
-  if( !ctx->h_gtime ) {
-    HIPCHK( hipHostMalloc( (void **)&ctx->h_gtime, ( fdgpu_ed25519_ctx_t::NGT + 1 ) * 2 * sizeof(unsigned long), hipHostMallocDefault ), -2 );
-    HIPCHK( hipHostGetDevicePointer( (void **)&ctx->d_gtime, (void *)ctx->h_gtime, 0 ), -2 );
-  }
+  if( !ctx->h_gtime )
+    HIPCHK( ctx_pin_alloc( ctx, &ctx->h_gtime, ( FD_NGT + 1 ) * 2 * sizeof(unsigned long), &ctx->d_gtime ), -2 );
   if( !ctx->gstream ) {
     /* the copies bound how long a frag stays exposed to a lapping producer: the highest stream
        priority, so the dispatcher starts them ahead of queued verify work as CU slots free up */
@@ -3691,15 +3681,15 @@ static long gather_prep( fdgpu_ed25519_ctx_t * ctx, fd_slot & sl, fd_gargs * a )
   /* time this gather if a ring entry is free (the ring is drained as gathers complete) */
   unsigned long * gt = NULL;
   gather_times( ctx, fdgpu_ed25519_gathered( ctx ) );
-  if( ctx->gt_tail - ctx->gt_head < fdgpu_ed25519_ctx_t::NGT ) {
-    unsigned long i = ctx->gt_tail % fdgpu_ed25519_ctx_t::NGT;
+  if( ctx->gt_tail - ctx->gt_head < FD_NGT ) {
+    unsigned long i = ctx->gt_tail % FD_NGT;
     ctx->h_gtime[ 2*i ] = 0UL; ctx->h_gtime[ 2*i + 1 ] = 0UL;
     ctx->gt[i].target = target; ctx->gt[i].t_launch = fd_now_ns();
     __atomic_store_n( &ctx->gt[i].t_issue, 0UL, __ATOMIC_RELAXED );
     ctx->gt_tail++;
     gt = ctx->d_gtime + 2*i;
     ctx->last_gt = (long)i;
-  } else { gt = ctx->d_gtime + 2*fdgpu_ed25519_ctx_t::NGT; ctx->last_gt = -1; }   /* untimed: a scratch entry */
+  } else { gt = ctx->d_gtime + 2*FD_NGT; ctx->last_gt = -1; }   /* untimed: a scratch entry */
   a->g = sl.g_dev + sl.gathered; a->n = (u32)n; a->d_payload = sl.d_payload;
   a->wb = ctx->gather_nowb == 0 && !sl.per_rec ? sl.ref_dev + sl.ref_lo : (unsigned char *)NULL;
   a->ovr = sl.d_ovr + sl.gathered; a->target = target; a->gt = gt; a->gti = ctx->last_gt;
@@ -3712,7 +3702,7 @@ static int gather_issue( fdgpu_ed25519_ctx_t * ctx, fd_gargs const * a ) {
   if( a->gti >= 0 ) __atomic_store_n( &ctx->gt[ a->gti ].t_issue, fd_now_ns(), __ATOMIC_RELEASE );
   hipLaunchKernelGGL( ( rpb == 1UL ? fd_gather_kernel<1> : fd_gather_kernel<4> ), dim3( (unsigned)( ( a->n + rpb - 1UL ) / rpb ) ),
                       dim3( 64UL * rpb ), 0, ctx->gstream, a->g, a->n, a->d_payload, a->wb, a->ovr, ctx->d_gcnt,
-                      (unsigned long *)( ctx->d_flag + fdgpu_ed25519_ctx_t::NSLOT + 1 ), a->target, a->gt );
+                      (unsigned long *)( ctx->d_flag + FD_NSLOT + 1 ), a->target, a->gt );
   HIPCHK( hipGetLastError(), -2 );
   return 0;
 }
@@ -3735,9 +3725,9 @@ struct fd_lcmd {
   fd_gargs              g;
 };
 
+#define FD_NCMD 512
 struct fdgpu_launcher {
-  enum { NCMD = 512 };
-  fd_lcmd                    cmd[ NCMD ];
+  fd_lcmd                    cmd[ FD_NCMD ];
   alignas(64) std::atomic<unsigned long> tail{ 0 };   /* written by the queueing thread */
   alignas(64) std::atomic<unsigned long> head{ 0 };   /* written by the launch thread */
   alignas(64) std::atomic<int>           stop{ 0 };
@@ -3764,7 +3754,7 @@ static void launcher_main( fdgpu_launcher_t * L ) {
       continue;
     }
     if( t - h > L->depth_max ) L->depth_max = t - h;
-    fd_lcmd const & c = L->cmd[ h % fdgpu_launcher::NCMD ];
+    fd_lcmd const & c = L->cmd[ h % FD_NCMD ];
     unsigned long t0 = fd_now_ns();
     if( !__atomic_load_n( &c.ctx->fault, __ATOMIC_ACQUIRE ) ) {
       int rc;
@@ -3786,11 +3776,11 @@ static void launcher_main( fdgpu_launcher_t * L ) {
 
 static void launcher_push( fdgpu_launcher_t * L, fd_lcmd const & c ) {
   unsigned long t = L->tail.load( std::memory_order_relaxed );
-  if( t - L->head.load( std::memory_order_acquire ) >= fdgpu_launcher::NCMD ) {
+  if( t - L->head.load( std::memory_order_acquire ) >= FD_NCMD ) {
     L->full_waits++;
-    while( t - L->head.load( std::memory_order_acquire ) >= fdgpu_launcher::NCMD ) __builtin_ia32_pause();
+    while( t - L->head.load( std::memory_order_acquire ) >= FD_NCMD ) __builtin_ia32_pause();
   }
-  L->cmd[ t % fdgpu_launcher::NCMD ] = c;
+  L->cmd[ t % FD_NCMD ] = c;
   L->tail.store( t + 1, std::memory_order_release );
 }
 
@@ -3859,14 +3849,6 @@ static long gather_launch( fdgpu_ed25519_ctx_t * ctx, fd_slot & sl ) {
   }
   if( gather_issue( ctx, &c.g ) ) return -2;
   return n;
-}
-
-static int slot_launch_( fdgpu_ed25519_ctx_t * ctx, int i );
-static int slot_launch( fdgpu_ed25519_ctx_t * ctx, int i ) {
-  unsigned long t0 = fd_now_ns();
-  int rc = slot_launch_( ctx, i );
-  ctx->launch_ns += fd_now_ns() - t0;
-  return rc;
 }
 
 /* the runtime calls of slot i's batch, in stream order (token: the value fd_done_kernel stores; g: the
@@ -3944,12 +3926,18 @@ static int slot_launch_( fdgpu_ed25519_ctx_t * ctx, int i ) {
   ctx->inflight.push_back( i );
   return 0;
 }
+static int slot_launch( fdgpu_ed25519_ctx_t * ctx, int i ) {
+  unsigned long t0 = fd_now_ns();
+  int rc = slot_launch_( ctx, i );
+  ctx->launch_ns += fd_now_ns() - t0;
+  return rc;
+}
 
 /* make ctx->cur a free slot; -2 if every slot is in flight, -3 if its
    buffers cannot be allocated */
 static int next_free( fdgpu_ed25519_ctx_t * ctx ) {
-  for( int k=0; k<fdgpu_ed25519_ctx_t::NSLOT; k++ ) {
-    int i = (ctx->cur + k) % fdgpu_ed25519_ctx_t::NSLOT;
+  for( int k=0; k<FD_NSLOT; k++ ) {
+    int i = (ctx->cur + k) % FD_NSLOT;
     if( ctx->slot[i].state==0 ) {
       if( slot_bufs( ctx, i ) ) return -3;
       ctx->cur = i; return 0;
@@ -4011,18 +3999,14 @@ fdgpu_ed25519_submit( fdgpu_ed25519_ctx_t * ctx, unsigned char const * payload, 
 static int slot_raw_bufs( fdgpu_ed25519_ctx_t * ctx, fd_slot * sl ) {
   if( sl->h_img ) return 0;
   HIPCHK( hipSetDevice( ctx->device ), -3 );
-  HIPCHK( hipHostMalloc( (void **)&sl->h_img, ctx->max_txn * FDGPU_TXN_IMG_STRIDE, hipHostMallocDefault ), -3 );
-  HIPCHK( hipHostMalloc( (void **)&sl->h_fp, ctx->max_txn * sizeof(unsigned short), hipHostMallocDefault ), -3 );
-  HIPCHK( hipMalloc( (void **)&sl->d_img, ctx->max_txn * FDGPU_TXN_IMG_STRIDE ), -3 );
-  HIPCHK( hipMalloc( (void **)&sl->d_fp, ctx->max_txn * sizeof(unsigned short) ), -3 );
-  HIPCHK( hipHostMalloc( (void **)&sl->h_dtag, ctx->max_txn * sizeof(unsigned long), hipHostMallocDefault ), -3 );
-  HIPCHK( hipMalloc( (void **)&sl->d_dtag, ctx->max_txn * sizeof(unsigned long) ), -3 );
-  HIPCHK( hipHostMalloc( (void **)&sl->h_gat, ctx->max_txn * sizeof(fd_gather), hipHostMallocDefault ), -3 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl->g_dev, (void *)sl->h_gat, 0 ), -3 );
-  HIPCHK( hipMalloc( (void **)&sl->d_ovr, ctx->max_txn ), -3 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl->hd_fp, (void *)sl->h_fp, 0 ), -3 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl->hd_dtag, (void *)sl->h_dtag, 0 ), -3 );
-  HIPCHK( hipHostGetDevicePointer( (void **)&sl->hd_img, (void *)sl->h_img, 0 ), -3 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl->h_img, ctx->max_txn * FDGPU_TXN_IMG_STRIDE, &sl->hd_img ), -3 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl->h_fp, ctx->max_txn * sizeof(unsigned short), &sl->hd_fp ), -3 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl->d_img, ctx->max_txn * FDGPU_TXN_IMG_STRIDE ), -3 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl->d_fp, ctx->max_txn * sizeof(unsigned short) ), -3 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl->h_dtag, ctx->max_txn * sizeof(unsigned long), &sl->hd_dtag ), -3 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl->d_dtag, ctx->max_txn * sizeof(unsigned long) ), -3 );
+  HIPCHK( ctx_pin_alloc( ctx, &sl->h_gat, ctx->max_txn * sizeof(fd_gather), &sl->g_dev ), -3 );
+  HIPCHK( ctx_dev_alloc( ctx, &sl->d_ovr, ctx->max_txn ), -3 );
   return 0;
 }
 
@@ -4031,7 +4015,7 @@ static int slot_raw_bufs( fdgpu_ed25519_ctx_t * ctx, fd_slot * sl ) {
 extern "C" int
 fdgpu_ed25519_prepare( fdgpu_ed25519_ctx_t * ctx, int raw ) {
   if( !ctx ) return -1;
-  for( int i=0; i<fdgpu_ed25519_ctx_t::NSLOT; i++ ) {
+  for( int i=0; i<FD_NSLOT; i++ ) {
     if( slot_bufs( ctx, i ) ) return -3;
     if( raw && slot_raw_bufs( ctx, &ctx->slot[i] ) ) return -3;
   }
@@ -4039,20 +4023,66 @@ fdgpu_ed25519_prepare( fdgpu_ed25519_ctx_t * ctx, int raw ) {
   return 0;
 }
 
+extern "C" void
+fdgpu_ed25519_ctx_delete( fdgpu_ed25519_ctx_t * ctx ) {
+  if( !ctx ) return;
+  (void)hipSetDevice( ctx->device );
+  if( ctx->launcher ) launcher_drain( ctx->launcher );   /* its queued calls are made before the streams drain */
+  /* every stream of the context drains before anything is freed: gathers of a slot that was still filling
+     (early copies, never launched) read its pinned descriptors and write its arena on the gather stream */
+  if( ctx->gstream ) (void)hipStreamSynchronize( ctx->gstream );
+  if( ctx->cstream ) (void)hipStreamSynchronize( ctx->cstream );
+  if( ctx->stream ) (void)hipStreamSynchronize( ctx->stream );
+  for( void * p : ctx->dev_mem ) (void)hipFree( p );
+  for( void * p : ctx->pin_mem ) (void)hipHostFree( p );
+  for( int i=0; i<5; i++ ) if( ctx->ev[i] ) (void)hipEventDestroy( ctx->ev[i] );
+  for( int r=0; r<FD_NRING; r++ ) for( int i=0; i<5; i++ ) if( ctx->ring[r][i] ) (void)hipEventDestroy( ctx->ring[r][i] );
+  for( int i=0; i<FD_NSLOT; i++ ) if( ctx->slot[i].done ) (void)hipEventDestroy( ctx->slot[i].done );
+  if( ctx->cstream ) { (void)hipStreamSynchronize( ctx->cstream ); (void)hipStreamDestroy( ctx->cstream ); }
+  if( ctx->gstream ) { (void)hipStreamSynchronize( ctx->gstream ); (void)hipStreamDestroy( ctx->gstream ); }
+  if( ctx->gev ) (void)hipEventDestroy( ctx->gev );
+  for( unsigned long i=0; i<FD_PIPE_MAX; i++ ) if( ctx->pipe_ev[i] ) (void)hipEventDestroy( ctx->pipe_ev[i] );
+  if( ctx->stream ) (void)hipStreamDestroy( ctx->stream );
+  delete ctx;
+}
+
+extern "C" fdgpu_ed25519_ctx_t *
+fdgpu_ed25519_ctx_new( int device, unsigned long max_txn, unsigned long max_sig,
+                       unsigned long max_payload_bytes, int semantics ) {
+  if( max_txn==0 || max_txn >= (1UL<<24) || max_sig==0 || max_sig >= (1UL<<31) ) { fd_err = "bad sizes"; return NULL; }
+  if( semantics!=FDGPU_SEMANTICS_AVX512 && semantics!=FDGPU_SEMANTICS_REF ) { fd_err = "bad semantics"; return NULL; }
+  HIPCHK( hipSetDevice( device ), NULL );
+  fdgpu_ed25519_ctx_t * ctx = new fdgpu_ed25519_ctx_t();
+  if( ctx_init( ctx, device, max_txn, max_sig, max_payload_bytes, semantics ) ) {
+    std::string err = fd_err;
+    fdgpu_ed25519_ctx_delete( ctx );
+    fd_err = err;
+    return NULL;
+  }
+  return ctx;
+}
+
+/* one more raw record in the filling slot, its payload at arena offset off; the caller accounts the arena */
+static inline fdgpu_txn_raw_t &
+raw_append( fd_slot * sl, size_t off, unsigned short payload_sz, unsigned lanes, unsigned long tag ) {
+  fdgpu_txn_raw_t & r = ((fdgpu_txn_raw_t *)sl->h_desc)[ sl->txn_cnt ];
+  r.payload_off = (unsigned)off; r.sig_base = (unsigned)sl->sig_cnt; r.payload_sz = payload_sz; r.sig_lanes = (unsigned char)lanes;
+  sl->h_tags[ sl->txn_cnt ] = tag;
+  sl->txn_cnt++; sl->sig_cnt += lanes;
+  return r;
+}
+
 extern "C" int
 fdgpu_ed25519_submit_raw( fdgpu_ed25519_ctx_t * ctx, unsigned char const * payload, unsigned short payload_sz,
                           unsigned long tag ) {
-  unsigned b0 = payload_sz ? payload[0] : 0u;
-  unsigned lanes = ( b0 >= 1u && b0 <= 16u ) ? b0 : 0u;
+  unsigned lanes = raw_lanes( payload, payload_sz );
   int rc; fd_slot * sl = slot_for( ctx, payload_sz, lanes, 1, &rc );
   if( !sl ) return rc;
   if( slot_raw_bufs( ctx, sl ) ) return -3;
   size_t off = sl->payload_used;
   memcpy( sl->h_payload + off, payload, payload_sz );
-  fdgpu_txn_raw_t & r = ((fdgpu_txn_raw_t *)sl->h_desc)[ sl->txn_cnt ];
-  r.payload_off = (unsigned)off; r.sig_base = (unsigned)sl->sig_cnt; r.payload_sz = payload_sz; r.sig_lanes = (unsigned char)lanes;
-  sl->h_tags[ sl->txn_cnt ] = tag;
-  sl->txn_cnt++; sl->sig_cnt += lanes; sl->payload_used = (off + payload_sz + 7) & ~(size_t)7;
+  raw_append( sl, off, payload_sz, lanes, tag );
+  sl->payload_used = (off + payload_sz + 7) & ~(size_t)7;
   return 0;
 }
 
@@ -4065,8 +4095,7 @@ fdgpu_ed25519_submit_raw( fdgpu_ed25519_ctx_t * ctx, unsigned char const * paylo
 extern "C" int
 fdgpu_ed25519_submit_raw_ref( fdgpu_ed25519_ctx_t * ctx, unsigned char const * base, unsigned char const * payload,
                               unsigned short payload_sz, unsigned long tag ) {
-  unsigned b0 = payload_sz ? payload[0] : 0u;
-  unsigned lanes = ( b0 >= 1u && b0 <= 16u ) ? b0 : 0u;
+  unsigned lanes = raw_lanes( payload, payload_sz );
   size_t off = (size_t)( payload - base );
   int rc; fd_slot * sl = slot_for( ctx, payload_sz, lanes, 2, &rc );
   if( !sl ) return rc;
@@ -4076,29 +4105,12 @@ fdgpu_ed25519_submit_raw_ref( fdgpu_ed25519_ctx_t * ctx, unsigned char const * b
   }
   if( slot_raw_bufs( ctx, sl ) ) return -3;
   if( !sl->txn_cnt ) { sl->ref_base = base; sl->ref_lo = off; }
-  fdgpu_txn_raw_t & r = ((fdgpu_txn_raw_t *)sl->h_desc)[ sl->txn_cnt ];
-  r.payload_off = (unsigned)( off - sl->ref_lo ); r.sig_base = (unsigned)sl->sig_cnt; r.payload_sz = payload_sz;
-  r.sig_lanes = (unsigned char)lanes;
-  sl->h_tags[ sl->txn_cnt ] = tag;
-  sl->txn_cnt++; sl->sig_cnt += lanes;
+  raw_append( sl, off - sl->ref_lo, payload_sz, lanes, tag );
   sl->ref_hi = off + payload_sz; sl->payload_used = sl->ref_hi - sl->ref_lo;
   return 0;
 }
 
-/* Host regions the GPU may read or write directly (fdgpu_host_alloc
-   allocations and fdgpu_host_register-ed ranges): host base -> device
-   address, for the gather path. */
-/* A fixed table read without a lock (every tile thread looks its frags up
-   here in during_frag; a global mutex there was contended by all of them):
-   writers (register / unregister, rare) serialise on a mutex, fill an
-   entry's fields and then publish it with a release store of its size; a
-   removed entry's size drops to 0 first. */
-#define FD_REGION_MAX 256
-struct fd_region { unsigned char const * h; unsigned char * d; std::atomic<unsigned long> sz; int refs, shared; };
-static std::mutex g_reg_mu;
-static fd_region g_regions[ FD_REGION_MAX ];
-static std::atomic<int> g_region_cnt{ 0 };
-
+/* The writers of the region table (g_regions, above region_dev) */
 static void region_add_locked( void * h, void * d, unsigned long sz ) {
   int n = g_region_cnt.load( std::memory_order_relaxed ), i = 0;
   while( i < n && g_regions[i].sz.load( std::memory_order_relaxed ) ) i++;     /* reuse a removed entry */
@@ -4123,26 +4135,6 @@ static void region_del( void * h ) {
   int i = region_find_locked( h );
   if( i >= 0 ) g_regions[i].sz.store( 0UL, std::memory_order_release );
 }
-/* device address of [p, p+sz) if it lies inside one registered region, else NULL */
-static unsigned char * region_dev( void const * p, unsigned long sz ) {
-  unsigned char const * q = (unsigned char const *)p;
-  /* a tile's frags come from one region: try the thread's last hit first (re-validated like
-     any entry, so a removed or reused entry is never trusted) */
-  static thread_local int hint = 0;
-  int n = g_region_cnt.load( std::memory_order_acquire );
-  if( hint < n ) {
-    unsigned long rs = g_regions[hint].sz.load( std::memory_order_acquire );
-    unsigned char const * h = g_regions[hint].h;
-    if( rs && q >= h && q + sz <= h + rs ) return g_regions[hint].d + ( q - h );
-  }
-  for( int i=0; i<n; i++ ) {
-    unsigned long rs = g_regions[i].sz.load( std::memory_order_acquire );
-    unsigned char const * h = g_regions[i].h;
-    if( rs && q >= h && q + sz <= h + rs ) { hint = i; return g_regions[i].d + ( q - h ); }
-  }
-  return NULL;
-}
-
 /* the registered region holding p: its host base, size and device base (0), or -1 */
 extern "C" int
 fdgpu_host_region( void const * p, void ** base, unsigned long * sz, void ** dev_base ) {
@@ -4241,66 +4233,8 @@ fdgpu_device_numa_node( int device ) {
 static int submit_gather( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * dsrc,
                           unsigned char * dst_base, unsigned char * dst, unsigned long csz, unsigned short payload_off,
                           unsigned short payload_sz, unsigned long tag, unsigned char const * dseq, unsigned long seq,
-                          unsigned flags );
-
-extern "C" int
-fdgpu_ed25519_submit_raw_gather_chk( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char * dst_base,
-                                     unsigned char * dst, unsigned short copy_sz, unsigned short payload_off,
-                                     unsigned short payload_sz, unsigned long tag, unsigned long const * seq_addr,
-                                     unsigned long seq ) {
-  if( (unsigned)payload_off + payload_sz > copy_sz || ( (uintptr_t)src & 15 ) || ( (uintptr_t)( dst - dst_base ) & 15 ) ||
-      ( ctx->rec_fp_off >= 0 && ( payload_off > 255u || (unsigned)ctx->rec_fp_off + 2u > payload_off ) ) ||
-      ( (uintptr_t)seq_addr & 7 ) ) {
-    fd_err = "fdgpu_ed25519_submit_raw_gather: bad record"; return -1;
-  }
-  unsigned long csz = ( (unsigned long)copy_sz + 15UL ) & ~15UL;
-  unsigned char * dsrc = region_dev( src, csz );
-  if( !dsrc ) { fd_err = "fdgpu_ed25519_submit_raw_gather: src not in a registered region"; return -3; }
-  unsigned char * dseq = NULL;
-  if( seq_addr && !( dseq = region_dev( seq_addr, sizeof(unsigned long) ) ) ) {
-    fd_err = "fdgpu_ed25519_submit_raw_gather: seq_addr not in a registered region"; return -3;
-  }
-  return submit_gather( ctx, src, dsrc, dst_base, dst, csz, payload_off, payload_sz, tag, dseq, seq, 0u );
-}
-
-/* the same with the device addresses of src and seq_addr already known to the caller (a tile that
-   translated its in link's regions once, fdgpu_host_dev_ptr): no region lookup per frag */
-extern "C" int
-fdgpu_ed25519_submit_raw_gather_dev( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * src_dev,
-                                     unsigned char * dst_base, unsigned char * dst, unsigned short copy_sz,
-                                     unsigned short payload_off, unsigned short payload_sz, unsigned long tag,
-                                     unsigned long const * seq_dev, unsigned long seq ) {
-  if( (unsigned)payload_off + payload_sz > copy_sz || ( (uintptr_t)src & 15 ) || ( (uintptr_t)src_dev & 15 ) ||
-      ( (uintptr_t)( dst - dst_base ) & 15 ) ||
-      ( ctx->rec_fp_off >= 0 && ( payload_off > 255u || (unsigned)ctx->rec_fp_off + 2u > payload_off ) ) ||
-      ( (uintptr_t)seq_dev & 7 ) ) {
-    fd_err = "fdgpu_ed25519_submit_raw_gather: bad record"; return -1;
-  }
-  return submit_gather( ctx, src, src_dev, dst_base, dst, ( (unsigned long)copy_sz + 15UL ) & ~15UL, payload_off,
-                        payload_sz, tag, (unsigned char const *)seq_dev, seq, 0u );
-}
-
-extern "C" int
-fdgpu_ed25519_submit_raw_gather_dev_f( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * src_dev,
-                                       unsigned char * dst_base, unsigned char * dst, unsigned short copy_sz,
-                                       unsigned short payload_off, unsigned short payload_sz, unsigned long tag,
-                                       unsigned long const * seq_dev, unsigned long seq, unsigned flags ) {
-  if( (unsigned)payload_off + payload_sz > copy_sz || ( (uintptr_t)src & 15 ) || ( (uintptr_t)src_dev & 15 ) ||
-      ( (uintptr_t)( dst - dst_base ) & 15 ) ||
-      ( ctx->rec_fp_off >= 0 && ( payload_off > 255u || (unsigned)ctx->rec_fp_off + 2u > payload_off ) ) ||
-      ( (uintptr_t)seq_dev & 7 ) || ( flags & ~(unsigned)FDGPU_GATHER_NO_WRITEBACK ) ) {
-    fd_err = "fdgpu_ed25519_submit_raw_gather: bad record"; return -1;
-  }
-  return submit_gather( ctx, src, src_dev, dst_base, dst, ( (unsigned long)copy_sz + 15UL ) & ~15UL, payload_off,
-                        payload_sz, tag, (unsigned char const *)seq_dev, seq, flags );
-}
-
-static int submit_gather( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * dsrc,
-                          unsigned char * dst_base, unsigned char * dst, unsigned long csz, unsigned short payload_off,
-                          unsigned short payload_sz, unsigned long tag, unsigned char const * dseq, unsigned long seq,
                           unsigned flags ) {
-  unsigned b0 = payload_sz ? src[ payload_off ] : 0u;
-  unsigned lanes = ( b0 >= 1u && b0 <= 16u ) ? b0 : 0u;
+  unsigned lanes = raw_lanes( src + payload_off, payload_sz );
   /* per-record (dst_base NULL): the record goes back to dst_dev, a place of its own; its arena offset is
      the next free one of the batch.  Else its arena offset mirrors its offset in the batch's out region. */
   int per_rec = !dst_base;
@@ -4324,12 +4258,10 @@ static int submit_gather( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, 
     }
   }
   if( per_rec ) off = sl->ref_hi;                /* (arena offsets stay 16-B aligned: csz is) */
-  fdgpu_txn_raw_t & r = ((fdgpu_txn_raw_t *)sl->h_desc)[ sl->txn_cnt ];
-  r.payload_off = (unsigned)( off - sl->ref_lo + payload_off ); r.sig_base = (unsigned)sl->sig_cnt;
-  r.payload_sz = payload_sz; r.sig_lanes = (unsigned char)lanes;
+  fd_gather & g = sl->h_gat[ sl->txn_cnt ];
+  fdgpu_txn_raw_t & r = raw_append( sl, off - sl->ref_lo + payload_off, payload_sz, lanes, tag );
   r._pad[0] = (unsigned char)payload_off;      /* fd_img_scatter_kernel finds the record header from it */
   r._pad[1] = (unsigned char)( ( flags >> 8 ) & 15u );   /* its HA dedup seed (FDGPU_GATHER_SEED) */
-  fd_gather & g = sl->h_gat[ sl->txn_cnt ];
   g.src = (unsigned long)dsrc; g.dst = (unsigned)( off - sl->ref_lo );
   /* a per-record batch writes its records back at the gather unless the write-back is off or deferred to the
      finish kernel (fdgpu_debug_opts_t.gather_no_writeback, whose A/B applies to both forms) */
@@ -4337,26 +4269,81 @@ static int submit_gather( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, 
   g.sz = (unsigned)csz | ( nowb ? 0x80000000u : 0u );
   g.seq_addr = (unsigned long)dseq; g.seq = seq;
   g.wb = per_rec ? (unsigned long)dst : 0UL;
-  sl->h_tags[ sl->txn_cnt ] = tag;
-  sl->txn_cnt++; sl->sig_cnt += lanes;
   sl->ref_hi = off + csz; sl->payload_used = sl->ref_hi - sl->ref_lo;
   return 0;
 }
 
+/* The record check of every gathered submit, on the tile's thread once per frag: the payload inside the
+   copied bytes; src, its device view and the record's place (place: its offset in the out region, or in the
+   per-record form its device address, which must be given) 16-byte aligned; the seq word 8-byte aligned; the
+   footprint field (fdgpu_ed25519_set_record_fp_off) inside the header ahead of the payload; no flag outside
+   flags_ok.  src_dev is NULL where the caller has not looked it up yet.  0, or -1 with fd_err set. */
+static inline int
+gather_check( fdgpu_ed25519_ctx_t const * ctx, void const * src, void const * src_dev, uintptr_t place, int per_rec,
+              void const * seq, unsigned copy_sz, unsigned payload_off, unsigned payload_sz, unsigned flags,
+              unsigned flags_ok ) {
+  if( payload_off + payload_sz > copy_sz || ( (uintptr_t)src & 15 ) || ( (uintptr_t)src_dev & 15 ) ||
+      ( per_rec && !place ) || ( place & 15 ) ||
+      ( ctx->rec_fp_off >= 0 && ( payload_off > 255u || (unsigned)ctx->rec_fp_off + 2u > payload_off ) ) ||
+      ( (uintptr_t)seq & 7 ) || ( flags & ~flags_ok ) ) {
+    fd_err = per_rec ? "fdgpu_ed25519_submit_raw_gather_to: bad record" : "fdgpu_ed25519_submit_raw_gather: bad record";
+    return -1;
+  }
+  return 0;
+}
+#define FD_GATHER_CSZ( copy_sz ) ( ( (unsigned long)(copy_sz) + 15UL ) & ~15UL )   /* the bytes copied: whole 16-B chunks */
+
+extern "C" int
+fdgpu_ed25519_submit_raw_gather_chk( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char * dst_base,
+                                     unsigned char * dst, unsigned short copy_sz, unsigned short payload_off,
+                                     unsigned short payload_sz, unsigned long tag, unsigned long const * seq_addr,
+                                     unsigned long seq ) {
+  if( gather_check( ctx, src, NULL, (uintptr_t)( dst - dst_base ), 0, seq_addr, copy_sz, payload_off, payload_sz, 0u, 0u ) )
+    return -1;
+  unsigned long csz = FD_GATHER_CSZ( copy_sz );
+  unsigned char * dsrc = region_dev( src, csz );
+  if( !dsrc ) { fd_err = "fdgpu_ed25519_submit_raw_gather: src not in a registered region"; return -3; }
+  unsigned char * dseq = NULL;
+  if( seq_addr && !( dseq = region_dev( seq_addr, sizeof(unsigned long) ) ) ) {
+    fd_err = "fdgpu_ed25519_submit_raw_gather: seq_addr not in a registered region"; return -3;
+  }
+  return submit_gather( ctx, src, dsrc, dst_base, dst, csz, payload_off, payload_sz, tag, dseq, seq, 0u );
+}
+
+/* the same with the device addresses of src and seq_addr already known to the caller (a tile that
+   translated its in link's regions once, fdgpu_host_dev_ptr): no region lookup per frag.  The only flag
+   is FDGPU_GATHER_NO_WRITEBACK: a dedup seed goes with the per-record form alone. */
+extern "C" int
+fdgpu_ed25519_submit_raw_gather_dev_f( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * src_dev,
+                                       unsigned char * dst_base, unsigned char * dst, unsigned short copy_sz,
+                                       unsigned short payload_off, unsigned short payload_sz, unsigned long tag,
+                                       unsigned long const * seq_dev, unsigned long seq, unsigned flags ) {
+  if( gather_check( ctx, src, src_dev, (uintptr_t)( dst - dst_base ), 0, seq_dev, copy_sz, payload_off, payload_sz, flags,
+                    FDGPU_GATHER_NO_WRITEBACK ) ) return -1;
+  return submit_gather( ctx, src, src_dev, dst_base, dst, FD_GATHER_CSZ( copy_sz ), payload_off, payload_sz, tag,
+                        (unsigned char const *)seq_dev, seq, flags );
+}
+
+extern "C" int
+fdgpu_ed25519_submit_raw_gather_dev( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * src_dev,
+                                     unsigned char * dst_base, unsigned char * dst, unsigned short copy_sz,
+                                     unsigned short payload_off, unsigned short payload_sz, unsigned long tag,
+                                     unsigned long const * seq_dev, unsigned long seq ) {
+  return fdgpu_ed25519_submit_raw_gather_dev_f( ctx, src, src_dev, dst_base, dst, copy_sz, payload_off, payload_sz, tag,
+                                                seq_dev, seq, 0u );
+}
+
+/* the per-record form (dst_base NULL selects it in submit_gather; dst carries the device address), which
+   also admits a dedup seed (FDGPU_GATHER_SEED) */
 extern "C" int
 fdgpu_ed25519_submit_raw_gather_to( fdgpu_ed25519_ctx_t * ctx, unsigned char const * src, unsigned char const * src_dev,
                                     unsigned char * dst_dev, unsigned short copy_sz, unsigned short payload_off,
                                     unsigned short payload_sz, unsigned long tag, unsigned long const * seq_dev,
                                     unsigned long seq, unsigned flags ) {
-  if( (unsigned)payload_off + payload_sz > copy_sz || ( (uintptr_t)src & 15 ) || ( (uintptr_t)src_dev & 15 ) ||
-      !dst_dev || ( (uintptr_t)dst_dev & 15 ) ||
-      ( ctx->rec_fp_off >= 0 && ( payload_off > 255u || (unsigned)ctx->rec_fp_off + 2u > payload_off ) ) ||
-      ( (uintptr_t)seq_dev & 7 ) || ( flags & ~( (unsigned)FDGPU_GATHER_NO_WRITEBACK | 0xf00u ) ) ) {
-    fd_err = "fdgpu_ed25519_submit_raw_gather_to: bad record"; return -1;
-  }
-  /* (dst_base NULL selects the per-record form; dst carries the device address) */
-  return submit_gather( ctx, src, src_dev, NULL, dst_dev, ( (unsigned long)copy_sz + 15UL ) & ~15UL, payload_off,
-                        payload_sz, tag, (unsigned char const *)seq_dev, seq, flags );
+  if( gather_check( ctx, src, src_dev, (uintptr_t)dst_dev, 1, seq_dev, copy_sz, payload_off, payload_sz, flags,
+                    FDGPU_GATHER_NO_WRITEBACK | 0xf00u ) ) return -1;
+  return submit_gather( ctx, src, src_dev, NULL, dst_dev, FD_GATHER_CSZ( copy_sz ), payload_off, payload_sz, tag,
+                        (unsigned char const *)seq_dev, seq, flags );
 }
 
 extern "C" int
@@ -4380,7 +4367,7 @@ fdgpu_ed25519_gather( fdgpu_ed25519_ctx_t * ctx ) {
 
 extern "C" unsigned long
 fdgpu_ed25519_gathered( fdgpu_ed25519_ctx_t const * ctx ) {
-  unsigned long g = ctx->h_flag[ fdgpu_ed25519_ctx_t::NSLOT + 1 ];
+  unsigned long g = ctx->h_flag[ FD_NSLOT + 1 ];
   std::atomic_thread_fence( std::memory_order_acquire );
   return g;
 }
