@@ -33,7 +33,12 @@
    index, 128 doublings, or 64 over the high tables for a repeated key's
    signatures; base-point adds from the [0..32768]([2^e]B) affine tables
    (L2 / Infinity Cache resident).  fd_dsm_slow_kernel: what the walk's
-   first blocks left of the signatures without a short pair.
+   first blocks left of the signatures without a short pair.  A key with
+   FD_FB_MIN signatures in the batch is treated like the base point
+   (DESIGN 16): fd_keyclass_kernel picks those keys, fd_ftab_kernel builds
+   their comb tables, their signatures get no lattice reduction, no decode
+   of R and no -R table, walk 24 doublings in fd_dsmh_kernel's third body,
+   and the full-length path's R-check kernels compare P with R's bytes.
 
    Full-length throughput path (launch_full; half = 0).  fd_decode_kernel
    (A only), fd_hash_kernel (signed radix-16 digits of k, radix-2^16 of
@@ -123,6 +128,23 @@
 #define FD_KS_W    FD_LAT_SKEW_W     /* windows per part of a hot signature's c0 (fd_gpu_lattice.h) */
 #define FD_KS_NW   FD_LAT_SKEW_NW    /* windows stored for it: digA rows [0, 2 W + NW), digR rows [0, NW) */
 
+/* Fixed-base keys: a key with at least this many signatures in a batch gets comb tables of its own,
+   FD_FB_T tables of [1..FD_FB_E]( [2^(32 t)](-A) ) in affine precomputed form (96 B an entry, 96 KB a key), and its
+   signatures walk 24 doublings.  Reasoned, not measured: the tables cost about 1,100 field multiplies of wave
+   time per key (the chain of up to 224 doublings shared by 8 keys of a wave, two waves of entries with an
+   inversion each) and a signature saves about 880 / 64 of that, which puts the break-even near 80 signatures.
+   Measured (tools/keyfixed_mix.py): a batch of keys with exactly 64 signatures each loses 0.42 ms per
+   1M with the bound at 64, one of exactly 128 wins at 128 -- by 0.5 ms, with only half of its 8,192 keys under
+   FD_FB_CAP.  A build with -DFD_FB_MIN=... measures another bound. */
+#ifndef FD_FB_MIN
+#define FD_FB_MIN  128u
+#endif
+#define FD_FB_T    8
+#define FD_FB_E    128
+#define FD_FB_CAP  4096u              /* the most fixed-base keys of a batch (400 MB of tables); a key beyond stays hot */
+#define FD_FB_NONE 0xffffffffu        /* fidx[] of a representative whose key is not fixed-base */
+#define FD_PEND_FBREQ 5               /* per-signature code in flight: a fixed-base signature whose P's encoding != R's bytes */
+
 typedef signed char i8;
 
 /* ------------------------------------------------------------------ */
@@ -193,6 +215,33 @@ FD_DEV void atab_unpack( ge_cached & c, atab_raw const & r ) {
   fe_from_quads( c.Z,   r.q[4], r.q[5] );
   fe_from_quads( c.T2d, r.q[6], r.q[7] );
 }
+
+/* The order of a partitioned batch (fd_keysplit_kernel): order[] holds the nf fixed-base signatures from the front
+   (none unless the context has fixed-base keys), then the nh hot ones, and the cold ones from the back;
+   the decode, hash and walk kernels run one lane per place in it, in ceil(nf/256) fixed-base blocks, ceil(nh/256)
+   hot blocks and then the cold blocks (at most sg + 2 in all), so a wave -- a whole block -- is of one class.
+   b: the block's index among those.  cls: 2 fixed-base, 1 hot, 0 cold; j: the lane's rank in its class; col: its
+   place in order[].  Returns 0 for a lane beyond its part. */
+FD_DEV int ks_pos( u32 b, u32 nsig, u32 nf, u32 nh, u32 & col, u32 & j, int & cls ) {
+  u32 fb = ( nf + FD_WG - 1u ) / FD_WG, hb = ( nh + FD_WG - 1u ) / FD_WG;
+  cls = b < fb ? 2 : b < fb + hb ? 1 : 0;
+  j = ( cls==2 ? b : cls==1 ? b - fb : b - fb - hb ) * FD_WG + threadIdx.x;
+  col = cls==2 ? j : cls==1 ? nf + j : nsig - 1u - j;
+  return j < ( cls==2 ? nf : cls==1 ? nh : nsig - nf - nh );
+}
+/* The signature at that place.  With fixed-base keys the split cannot know where the hot segment starts, so it
+   lists the hot signatures in orderh[] and fd_hashh_kernel's hot lanes copy them to order[nf + j]: a kernel
+   launched after the hash reads order[] alone (orderh = NULL). */
+FD_DEV u32 ks_sig( u32 const * __restrict__ order, u32 const * __restrict__ orderh, u32 col, u32 j, int cls ) {
+  return ( orderh && cls==1 ) ? orderh[j] : order[col];
+}
+/* fd_keysplit_kernel's counters (kscnt[]): hot keys, hot signatures, cold signatures, fixed-base keys claimed
+   (may exceed the cap), fixed-base signatures */
+#define FD_KC_HOTK 0
+#define FD_KC_HOT  1
+#define FD_KC_COLD 2
+#define FD_KC_FBK  3
+#define FD_KC_FB   4
 
 /* ------------------------------------------------------------------ */
 
@@ -289,7 +338,12 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
                   u32 const *              __restrict__ ulist,
                   u32 *                    __restrict__ ucnt,
                   unsigned char *          __restrict__ astat,
-                  u32                                   ublk ) {
+                  u32                                   ublk,
+                  /* fixed-base keys: the R lanes run by place in the partition, none for a
+                     fixed-base signature (its R is compared undecoded); NULL: one R lane per signature */
+                  u32 const *              __restrict__ order,
+                  u32 const *              __restrict__ orderh,
+                  u32 const *              __restrict__ kscnt ) {
   u32 s, is_r;
   unsigned char * st;
   if( ulist ) {
@@ -309,6 +363,11 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
       }
       if( i >= cnt ) return;
       s = ulist[i]; is_r = 0u; st = astat + s;
+    } else if( order ) {
+      u32 col, j; int cls;
+      if( !ks_pos( blockIdx.x - ublk, nsig, kscnt[FD_KC_FB], kscnt[FD_KC_HOT], col, j, cls ) || cls==2 ) return;
+      s = ks_sig( order, orderh, col, j, cls ); is_r = 1u;
+      st = pstat + 2u*s + 1u;
     } else {
       s = ( blockIdx.x - ublk ) * FD_WG + threadIdx.x; is_r = 1u;
       if( s >= nsig ) return;
@@ -717,18 +776,6 @@ FD_DEV void hashh_one_q( unsigned char const * __restrict__ payload, fdgpu_txn_d
   }
 }
 
-/* Hot / cold order (fd_keysplit_kernel): the hot signatures fill order[] from the front, the cold ones from the
-   back, and the hash and walk kernels run one lane per place in it, in ceil(nh/256) hot blocks followed by the cold
-   blocks (at most sg + 1 in all), so a wave -- a whole block -- is all hot or all cold.  b: the block's index among
-   those.  Returns 0 for a lane beyond its part. */
-FD_DEV int ks_pos( u32 b, u32 nsig, u32 nh, u32 & col, int & hot ) {
-  u32 hb = ( nh + FD_WG - 1u ) / FD_WG;
-  hot = b < hb;
-  u32 j = ( hot ? b : b - hb ) * FD_WG + threadIdx.x;
-  col = hot ? j : nsig - 1u - j;
-  return j < ( hot ? nh : nsig - nh );
-}
-
 /* The high tables of hot key number hi: [1..8]( [2^(68 (part+1))](-A) ) in the -A table's entry format, at table
    index 2 hi + part of htab, from the representative's canonical affine A */
 template<int FM = FD_CARRY_FOLD>
@@ -763,6 +810,173 @@ FD_DEV void htab_build( uint4 * __restrict__ htab, u32 hi, u32 part, uint4 const
   }
 }
 
+/* ---- fixed-base keys ------------------------------------------
+   A key with FD_FB_MIN signatures in a batch is treated like the base point: its signatures are verified as
+     P = [S]B + [k](-A),  k = sum_{j<32} a_j 2^(8j),  S = sum_{i<16} b_i 2^(16i)   (signed digits)
+   from FD_FB_T tables per key, T_t = { [e]( [2^(32t)](-A) ) : e = 1..FD_FB_E }, and the base point's
+   [0..32768]( [2^(32t)]B ), in 24 doublings, and P's encoding is compared with R's 32 bytes by the full-length
+   path's R-check kernels: no lattice reduction, no decode of R, no -R table. */
+
+/* Hash role of a fixed-base signature at place col: the result code with R's check deferred (hash_one with
+   defer = 1: a small-order A parked as FD_PEND_ASMALL), R's bytes to Rraw[4 s] (the signature's own, unused Rxy
+   slot), the 32 signed radix-256 digits of k mod l to digA's rows [0, 32) and S's 16 digits to digB */
+FD_DEV void hashf_one( unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
+                       u32 const * __restrict__ map, u32 s, size_t n, int semantics, u32 pa,
+                       i8 * __restrict__ code_out, i8 * __restrict__ digA, short * __restrict__ digB,
+                       uint4 * __restrict__ Rraw, uint4 const * __restrict__ khash, u32 col ) {
+  fdgpu_txn_desc_t d; u32 j;
+  if( !sig_desc( desc, map, s, d, j ) ) { code_out[s] = FD_ED25519_ERR_SIG; return; }
+  unsigned char const * base = payload + d.payload_off;
+  u32 Sw[8];
+  fd_load_words<8>( Sw, base + d.signature_off + 64u*j + 32u );
+  int code = sc_is_canonical( Sw ) ? FD_ED25519_SUCCESS : FD_ED25519_ERR_SIG;
+  code = result_code( code, pa, 0u, semantics, 1 );
+  code_out[s] = (i8)code;
+  if( code != FD_ED25519_SUCCESS && code != FD_PEND_ASMALL ) return;
+  u32 Rw[8], Aw[8];
+  fd_load_words<8>( Rw, base + d.signature_off + 64u*j );
+  Rraw[4*(size_t)s]   = make_uint4( Rw[0], Rw[1], Rw[2], Rw[3] );
+  Rraw[4*(size_t)s+1] = make_uint4( Rw[4], Rw[5], Rw[6], Rw[7] );
+  if( code != FD_ED25519_SUCCESS ) return;
+  fd_load_words<8>( Aw, base + d.acct_addr_off + 32u*j );
+  u32 h[16], k[8];
+  if( khash ) khash_load( h, khash, s );
+  else fd_sha512_RAM( h, Rw, Aw, base + d.message_off, (u32)d.payload_sz - (u32)d.message_off );
+  sc_reduce( k, h );
+  i8 dk[ 32 ];
+  (void)fd_fb_recode( dk, k );                       /* (k < l: no carry out of the top digit) */
+#pragma unroll
+  for( int i=0; i<32; i++ ) digA[(size_t)i*n + col] = dk[i];
+  (void)store_digits_B( Sw, col, n, digB, 0, []( int ) { return 0; } );
+}
+
+/* P_t = [2^(32t)](-A) of fixed-base key fi in the -A table's entry format at fbase[8 fi + t], from the
+   representative's canonical affine A: one lane per (key, t), so the chain of up to 224 doublings is paid by 8
+   lanes of a key and not by the 1,024 that build its entries */
+template<int FM = FD_CARRY_FOLD>
+FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 t, uint4 const * __restrict__ Axy, u32 rep ) {
+  uint4 const * ap = Axy + (size_t)rep*4;
+  ge_p3 A;
+  fe_from_quads( A.X, ap[0], ap[1] );
+  fe_from_quads( A.Y, ap[2], ap[3] );
+  A.Z = fe_one();
+  fe_neg( A.X, A.X ); fe_wcarry( A.X, A.X );              /* -A */
+  fe_mul<FM>( A.T, A.X, A.Y );
+  int nd = 32*(int)t;
+#pragma unroll 1
+  for( int i=0; i<nd; i++ ) ge_p3_dbl<FM>( A, A );
+  ge_cached c;
+  ge_p3_to_cached<FM>( c, A );
+  uint4 * b = fbase + ( (size_t)fi * FD_FB_T + t ) * 8;
+  fe_store_packed( b + 0, c.YpX );
+  fe_store_packed( b + 2, c.YmX );
+  fe_store_packed( b + 4, c.Z   );
+  fe_store_packed( b + 6, c.T2d );
+}
+
+/* the identity in affine precomputed form (y+x = y-x = 1, 2dxy = 0), packed like a table entry: digit 0 */
+__device__ __attribute__(( aligned( 16 ) )) unsigned const fd_ptab_ident_w[ 24 ] = {
+  1u,0u,0u,0u, 0u,0u,0u,0u,  1u,0u,0u,0u, 0u,0u,0u,0u,  0u,0u,0u,0u, 0u,0u,0u,0u };
+
+/* entry e >= 1 of table t of fixed-base key fi: 6 uint4 (ypx, ymx, xy2d, canonical, packed 8x32) */
+FD_DEV size_t ftab_at( u32 fi, u32 t, u32 e ) {
+  return ( ( (size_t)fi * FD_FB_T + t ) * FD_FB_E + ( e - 1u ) ) * 6;
+}
+
+/* fd_ftab_kernel's two passes over a lane's eight points, written as recursions over the point's number so
+   that every index of the prefix array pf[] is a constant and the array stays in registers.
+   Pass 1, point I: Q += P_t, parked projective in its own entry (X, Y, Z: 96 B); pf[I] = Z_0 ... Z_I. */
+template<int I>
+FD_DEV void ftab_pass1( ge_p3 & Q, ge_cached const & pc, uint4 * __restrict__ ent, fe (&pf)[ 8 ] ) {
+  ge_p1p1 tt;
+  ge_add_cached( tt, Q, pc ); ge_p1p1_to_p3( Q, tt );
+  fe_store_packed( ent + 6*I + 0, Q.X );
+  fe_store_packed( ent + 6*I + 2, Q.Y );
+  fe_store_packed( ent + 6*I + 4, Q.Z );
+  if constexpr( I > 0 ) fe_mul( pf[I], pf[I-1], Q.Z ); else pf[0] = Q.Z;
+  if constexpr( I < 7 ) ftab_pass1<I+1>( Q, pc, ent, pf );
+}
+/* Pass 2, from point 7 down, inv = 1 / (Z_0 ... Z_I) on entry: 1/Z_I = inv pf[I-1], then the affine precomputed
+   entry (y+x, y-x, 2dxy) over the parked point */
+template<int I>
+FD_DEV void ftab_pass2( fe & inv, uint4 * __restrict__ ent, fe const (&pf)[ 8 ] ) {
+  fe X, Y, Z, zi, x, y, u;
+  fe_from_quads( X, ent[6*I+0], ent[6*I+1] );
+  fe_from_quads( Y, ent[6*I+2], ent[6*I+3] );
+  if constexpr( I > 0 ) {
+    fe_from_quads( Z, ent[6*I+4], ent[6*I+5] );
+    fe_mul( zi, inv, pf[I-1] ); fe_mul( inv, inv, Z );
+  } else zi = inv;
+  fe_mul( x, X, zi ); fe_mul( y, Y, zi );
+  fe_add( u, y, x ); fe_store_packed( ent + 6*I + 0, u );
+  fe_sub( u, y, x ); fe_store_packed( ent + 6*I + 2, u );
+  fe d2 = fe_d2();
+  fe_mul( u, x, y ); fe_mul( u, u, d2 ); fe_store_packed( ent + 6*I + 4, u );
+  if constexpr( I > 0 ) ftab_pass2<I-1>( inv, ent, pf );
+}
+
+/* The entries of the fixed-base keys' tables: 128 lanes per key (a workgroup holds two keys), lane (t, g) with
+   g = 0..15 builds entries 8g + 1 .. 8g + 8 of table t.  It starts at [8g]P_t by double-and-add over g's 4 bits
+   and three doublings, adds P_t eight times, and normalises its eight points with Montgomery's trick: the
+   product of its own eight Z, the products of the other lanes' through lane-shuffle prefix and suffix products
+   as in fd_rprod_kernel, one inversion per wave (every lane computes it: no lane of the wave has anything else
+   to do), then 1/Z_i = (prefix of the lane's Z below i) x (running inverse).  Blocks beyond the device-side count
+   of fixed-base keys return at once; a key that does not decode or has small order has no table (its
+   signatures' codes are final or parked before any walk). */
+__global__ void __launch_bounds__( FD_WG, 2 )          /* (two waves per SIMD asked for: the eight prefix products are 80 VGPRs) */
+fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 fcap, u32 const * __restrict__ flist,
+                unsigned char const * __restrict__ astat, uint4 const * __restrict__ fbase, uint4 * __restrict__ ftab ) {
+  u32 nk = kscnt[FD_KC_FBK]; nk = nk < fcap ? nk : fcap;
+  u32 fi = blockIdx.x * 2u + ( threadIdx.x >> 7 );
+  if( blockIdx.x * 2u >= nk ) return;                     /* (block-uniform) */
+  /* a wave is of one key: lanes of a key that is beyond the count, or has no table, skip the work together */
+  if( fi >= nk || ( astat[ flist[fi] ] & 7u ) ) return;
+  u32 t = ( threadIdx.x >> 4 ) & 7u, g = threadIdx.x & 15u;
+  int lane = (int)( threadIdx.x & 63u );
+  ge_cached pc;
+  {
+    atab_raw r; uint4 const * b = fbase + ( (size_t)fi * FD_FB_T + t ) * 8;
+#pragma unroll
+    for( int i=0; i<8; i++ ) r.q[i] = b[i];
+    atab_unpack( pc, r );
+  }
+  ge_p3 Q; ge_p3_identity( Q );
+  ge_p1p1 tt;
+#pragma unroll 1
+  for( int b=3; b>=0; b-- ) {                             /* [g]P_t */
+    ge_p3_dbl( Q, Q );
+    ge_add_cached( tt, Q, pc );
+    ge_p3 Qa; ge_p1p1_to_p3( Qa, tt );
+    int bit = (int)( ( g >> b ) & 1u );
+    fe_sel( Q.X, bit, Qa.X, Q.X ); fe_sel( Q.Y, bit, Qa.Y, Q.Y ); fe_sel( Q.Z, bit, Qa.Z, Q.Z ); fe_sel( Q.T, bit, Qa.T, Q.T );
+  }
+#pragma unroll 1
+  for( int b=0; b<3; b++ ) ge_p3_dbl( Q, Q );             /* [8g]P_t */
+  /* pass 1: the eight points, projective, parked in their own entries (X, Y, Z: 96 B), and the prefix products
+     of their Z */
+  fe pf[ 8 ];
+  uint4 * ent = ftab + ftab_at( fi, t, 8u*g + 1u );
+  ftab_pass1<0>( Q, pc, ent, pf );
+  /* the inverse of the lane's product: the wave's prefix and suffix products of the lanes' products, the wave's
+     total inverted, times the other lanes' product */
+  fe one = fe_one(), pre = pf[7], suf = pf[7], u;
+#pragma unroll 1
+  for( int d=1; d<64; d<<=1 ) {
+    fe_shfl_up( u, pre, d );   fe_sel( u, lane >= d, u, one );     fe_mul( pre, pre, u );
+    fe_shfl_down( u, suf, d ); fe_sel( u, lane + d < 64, u, one ); fe_mul( suf, suf, u );
+  }
+  fe o, e, tot, inv;
+  fe_shfl_up( o, pre, 1 );   fe_sel( o, lane > 0, o, one );
+  fe_shfl_down( e, suf, 1 ); fe_sel( e, lane < 63, e, one );
+  fe_mul( o, o, e );                                      /* the other lanes' product */
+#pragma unroll
+  for( int i=0; i<10; i++ ) tot.v[i] = (u32)__shfl( (int)pre.v[i], 63, 64 );
+  fe_invert( inv, tot );
+  fe_mul( inv, inv, o );                                  /* 1 / (Z_1 ... Z_8) of this lane */
+  /* pass 2, from the last point down: 1/Z_i, then the affine precomputed entry over the parked point */
+  ftab_pass2<7>( inv, ent, pf );
+}
+
 /* (no minimum waves per SIMD asked of the compiler: the lattice reduction sets 159 VGPRs, 3 waves) */
 template<int KS>
 __global__ void __launch_bounds__( FD_WG )
@@ -784,27 +998,50 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  u32 const *              __restrict__ arep,
                  unsigned char const *    __restrict__ astat,
                  /* KS (hot / cold partition, fd_keysplit_kernel): */
-                 u32 const *              __restrict__ order,    /* lane i of the walking blocks <-> signature order[i] */
-                 u32 const *              __restrict__ kscnt,    /* [0] hot keys, [1] hot signatures */
+                 u32 *                    __restrict__ order,    /* lane i of the walking blocks <-> signature order[i] */
+                 u32 const *              __restrict__ kscnt,    /* fd_keysplit_kernel's counters (FD_KC_*) */
                  u32 const *              __restrict__ hlist,    /* the hot keys' representatives */
                  uint4 const *            __restrict__ Axy,
                  uint4 *                  __restrict__ htab,     /* [hot key][2][8] entries: [1..8]([2^68](-A)), ([2^136](-A)) */
-                 u32                                   hblk ) {  /* blocks [0,hblk) build them: one lane per (key, part) */
+                 u32                                   hblk,     /* blocks [0,hblk) build them: one lane per (key, part) */
+                 /* fixed-base keys (orderh = NULL: none): */
+                 u32 const *              __restrict__ orderh,   /* the hot signatures as the split listed them */
+                 u32 const *              __restrict__ flist,    /* the fixed-base keys' representatives */
+                 uint4 *                  __restrict__ fbase,    /* [key][8] [2^(32t)](-A) */
+                 u32                                   fblk,     /* blocks [hblk,hblk+fblk) build them: one lane per (key, t) */
+                 u32                                   fcap,
+                 uint4 *                  __restrict__ Rraw ) {
   if( KS ) {
     if( blockIdx.x < hblk ) {
       /* dispatched first, so the chains of 68 and 136 doublings run beside the hash and not after it.  A key that
          does not decode or has small order builds nothing: its signatures' codes are final without a walk */
       u32 i = blockIdx.x * FD_WG + threadIdx.x;
-      if( ( i >> 1 ) >= kscnt[0] ) return;
+      if( ( i >> 1 ) >= kscnt[FD_KC_HOTK] ) return;
       u32 rep = hlist[ i >> 1 ];
       if( astat[rep] & 7u ) return;
       htab_build( htab, i >> 1, i & 1u, Axy, rep );
       return;
     }
-    u32 col; int hot;
-    if( !ks_pos( blockIdx.x - hblk, nsig, kscnt[1], col, hot ) ) return;
-    hashh_one<1>( payload, desc, map, order[col], nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt,
-                  khash, force_slow, htop, arep, astat, col, hot );
+    if( blockIdx.x < hblk + fblk ) {
+      /* likewise the fixed-base keys' chains of 32 t doublings, ahead of fd_ftab_kernel */
+      u32 i = ( blockIdx.x - hblk ) * FD_WG + threadIdx.x;
+      u32 nk = kscnt[FD_KC_FBK]; nk = nk < fcap ? nk : fcap;
+      if( ( i >> 3 ) >= nk ) return;
+      u32 rep = flist[ i >> 3 ];
+      if( astat[rep] & 7u ) return;
+      fbase_build( fbase, i >> 3, i & 7u, Axy, rep );
+      return;
+    }
+    u32 col, j; int cls;
+    if( !ks_pos( blockIdx.x - hblk - fblk, nsig, orderh ? kscnt[FD_KC_FB] : 0u, kscnt[FD_KC_HOT], col, j, cls ) ) return;
+    u32 s = ks_sig( order, orderh, col, j, cls );
+    if( cls==2 ) {
+      hashf_one( payload, desc, map, s, nsig, semantics, astat[ arep[s] ], code_out, digA, digB, Rraw, khash, col );
+      return;
+    }
+    if( orderh && cls==1 ) order[col] = s;                /* the hot segment of order[], for the kernels after this one */
+    hashh_one<1>( payload, desc, map, s, nsig, semantics, 1, pstat, code_out, digA, digR, digB, slow, slow_cnt,
+                  khash, force_slow, htop, arep, astat, col, cls==1 );
     return;
   }
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
@@ -1098,6 +1335,65 @@ FD_DEV int dsmh_hot( u32 s, u32 col, size_t n, int wtop, u32 sa, u32 hi,
   return fe_is_zero( P2.X ) & fe_eq( P2.Y, P2.Z );
 }
 
+/* The walk of a fixed-base signature: P = [S]B + [k](-A) from the key's tables (ftab, key fi) and
+   the base point's (btabf[t] = [0..32768]([2^(32t)]B)), in four steps at bit offsets 24, 16, 8 and 0 of each
+   32-bit span with 8 doublings between steps.  The step at offset 8r adds digit a_(4t+r) of k from table t for
+   t = 0..7, and the steps at offsets 16 and 0 also digit b_(2t+1), b_(2t) of S from btabf[t]: 32 + 16 affine
+   adds, 24 doublings.  Each 96-byte entry is gathered one add ahead.  P goes to Pbuf's column col for the R-check
+   kernels, as dsm_one( defer = 1 ) leaves it. */
+FD_DEV void ptab_fetch( uint4 r[ 6 ], uint4 const * p ) {
+#pragma unroll
+  for( int i=0; i<6; i++ ) r[i] = p[i];
+}
+template<int FM>
+FD_DEV void dsmf_one( u32 col, size_t n, u32 fi, uint4 const * __restrict__ ftab, uint4 const * __restrict__ btabf,
+                      i8 const * __restrict__ digA, short const * __restrict__ digB, u32 * __restrict__ Pbuf ) {
+  ge_p3 P; ge_p3_identity( P );
+  i8 const * dA = digA + col; short const * dB = digB + col;
+  uint4 ra[ 6 ], rb[ 6 ];
+#pragma unroll 1
+  for( int r=3; r>=0; r-- ) {
+    int na = ( r & 1 ) ? FD_FB_T : 2*FD_FB_T;          /* adds of this step: 8 from the key's tables, then 8 from B's */
+    int d = dA[ (size_t)r*n ];
+    ptab_fetch( ra, d ? ftab + ftab_at( fi, 0u, (u32)( d < 0 ? -d : d ) ) : (uint4 const *)fd_ptab_ident_w );
+#pragma unroll 1
+    for( int i=0; i<na; i++ ) {
+      int dn = 0;
+      if( i + 1 < na ) {                               /* the next add's entry, in flight during this one */
+        int i1 = i + 1;
+        if( i1 < FD_FB_T ) {
+          dn = dA[ (size_t)( 4*i1 + r )*n ];
+          ptab_fetch( rb, dn ? ftab + ftab_at( fi, (u32)i1, (u32)( dn < 0 ? -dn : dn ) ) : (uint4 const *)fd_ptab_ident_w );
+        } else {
+          int tb = i1 - FD_FB_T;
+          dn = dB[ (size_t)( 2*tb + ( r >> 1 ) )*n ];
+          ptab_fetch( rb, btabf + ( (size_t)tb * FD_BTAB_ENTRIES + (size_t)( dn < 0 ? -dn : dn ) ) * 6 );
+        }
+      }
+      ge_precomp q;
+      fe_from_quads( q.ypx,  ra[0], ra[1] );
+      fe_from_quads( q.ymx,  ra[2], ra[3] );
+      fe_from_quads( q.xy2d, ra[4], ra[5] );
+      ge_precomp_cneg( q, d < 0 );
+      ge_p1p1 t;
+      ge_add_precomp<FM>( t, P, q ); ge_p1p1_to_p3<FM>( P, t );
+#pragma unroll
+      for( int v=0; v<6; v++ ) ra[v] = rb[v];
+      d = dn;
+    }
+    if( r ) {
+      ge_p2 P2; P2.X = P.X; P2.Y = P.Y; P2.Z = P.Z;
+      ge_p1p1 t;
+#pragma unroll 1
+      for( int b=0; b<7; b++ ) { ge_dbl<FM>( t, P2 ); ge_p1p1_to_p2<FM>( P2, t ); }
+      ge_dbl<FM>( t, P2 ); ge_p1p1_to_p3<FM>( P, t );
+    }
+  }
+  fe_store_planar( Pbuf + col, n, P.X );
+  fe_store_planar( Pbuf + 10*n + col, n, P.Y );
+  fe_store_planar( Pbuf + 20*n + col, n, P.Z );
+}
+
 template<int FM, int KS = 0>
 __global__ void __launch_bounds__( FD_WG, FM ? FD_DSMH_MINW : 1 )
 fd_dsmh_kernel( u32                      nsig,
@@ -1123,7 +1419,12 @@ fd_dsmh_kernel( u32                      nsig,
                 u32 const *   __restrict__ kscnt,        /* [1] hot signatures */
                 u32 const *   __restrict__ hidx,         /* a hot representative's dense index */
                 uint4 const * __restrict__ htab,         /* the high tables (htab_build) */
-                uint4 const * __restrict__ btabh ) {     /* [0..32768](2^e B), e = 72, 140, 196 */
+                uint4 const * __restrict__ btabh,        /* [0..32768](2^e B), e = 72, 140, 196 */
+                /* fixed-base keys (fidx = NULL: none; the grid is then nslowblk + sg + 2 blocks): */
+                u32 const *   __restrict__ fidx,         /* a fixed-base representative's dense index */
+                uint4 const * __restrict__ ftab,         /* the keys' tables (fd_ftab_kernel) */
+                uint4 const * __restrict__ btabf,        /* [8][0..32768]([2^(32t)]B) */
+                u32 *         __restrict__ Pbuf ) {      /* P of a fixed-base signature, at its place */
   size_t n = nsig;
   if( blockIdx.x < nslowblk ) {
     /* the first blocks take the head of the slow list (full 253-bit walk,
@@ -1138,7 +1439,17 @@ fd_dsmh_kernel( u32                      nsig,
   }
   /* col: the lane's digit column -- the signature itself, or (KS) its place in the hot / cold order */
   u32 s, col; int in, hot = 0;
-  if( KS ) { in = ks_pos( blockIdx.x - nslowblk, nsig, kscnt[1], col, hot ); s = in ? order[col] : 0u; }
+  if( KS ) {
+    u32 j; int cls;
+    in = ks_pos( blockIdx.x - nslowblk, nsig, fidx ? kscnt[FD_KC_FB] : 0u, kscnt[FD_KC_HOT], col, j, cls );
+    s = in ? order[col] : 0u;
+    if( cls==2 ) {                                      /* (block-uniform) a fixed-base block: pending = SUCCESS so far */
+      if( in && code[s] == FD_ED25519_SUCCESS )
+        dsmf_one<FM>( col, n, fidx[ arep[s] ], ftab, btabf, (i8 const *)digA, digB, Pbuf );
+      return;
+    }
+    hot = cls==1;
+  }
   else { s = col = ( blockIdx.x - nslowblk ) * FD_WG + threadIdx.x; in = s < nsig; }
   /* a slow-list signature's code may already be final (SUCCESS) when this
      block starts: the flag, not the code, keeps it out */
@@ -1827,14 +2138,21 @@ fd_dsm8_kernel( u32                      nsig,
    Lanes without a pending verdict carry Z = 1. */
 __global__ void __launch_bounds__( FD_WG )
 fd_rprod_kernel( u32 nsig, i8 const * __restrict__ code, u32 const * __restrict__ Pbuf,
-                 u32 * __restrict__ Obuf, u32 * __restrict__ blk, u32 * __restrict__ slow_cnt ) {
+                 u32 * __restrict__ Obuf, u32 * __restrict__ blk, u32 * __restrict__ slow_cnt,
+                 /* the half-size path's fixed-base segment, else NULL: lane i takes the signature at
+                    place i of order[], i < *ocnt (a count on the device; the grid holds the worst case, blocks
+                    beyond it return at once), and P, the products and the list go by place */
+                 u32 const * __restrict__ order, u32 const * __restrict__ ocnt ) {
   __shared__ fe wtot[ FD_WG/64 ];
-  u32 s = blockIdx.x * FD_WG + threadIdx.x;
-  if( s == 0u ) *slow_cnt = 0u;                      /* fd_rcheck_kernel's append counter for this batch */
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i == 0u ) *slow_cnt = 0u;                      /* fd_rcheck_kernel's append counter for this batch */
+  u32 cnt = order ? *ocnt : nsig;
+  if( blockIdx.x * FD_WG >= cnt ) return;
+  u32 s = ( order && i < cnt ) ? order[i] : i;
   int lane = (int)( threadIdx.x & 63u ), w = (int)( threadIdx.x >> 6 );
   size_t n = nsig;
   fe one = fe_one(), z = one;
-  if( s < nsig && code[s]==FD_ED25519_SUCCESS ) fe_load_planar( z, Pbuf + 20*n + s, n );
+  if( i < cnt && code[s]==FD_ED25519_SUCCESS ) fe_load_planar( z, Pbuf + 20*n + i, n );
   fe pre = z, suf = z, t;
 #pragma unroll 1
   for( int d=1; d<64; d<<=1 ) {
@@ -1849,7 +2167,7 @@ fd_rprod_kernel( u32 nsig, i8 const * __restrict__ code, u32 const * __restrict_
   __syncthreads();
 #pragma unroll
   for( int v=0; v<FD_WG/64; v++ ) if( v != w ) { fe tv = wtot[v]; fe_mul( o, o, tv ); }
-  if( s < nsig ) fe_store_planar( Obuf + s, n, o );
+  if( i < cnt ) fe_store_planar( Obuf + i, n, o );
   if( threadIdx.x == 0 ) {
     fe b = wtot[0];
 #pragma unroll
@@ -1860,9 +2178,10 @@ fd_rprod_kernel( u32 nsig, i8 const * __restrict__ code, u32 const * __restrict_
 }
 
 __global__ void __launch_bounds__( FD_WG )
-fd_rinv_kernel( u32 nblk, u32 * __restrict__ blk ) {
+fd_rinv_kernel( u32 nblk, u32 * __restrict__ blk, u32 const * __restrict__ ocnt ) {   /* ocnt: as fd_rprod_kernel's */
   u32 b = blockIdx.x * FD_WG + threadIdx.x;
   if( b >= nblk ) return;
+  if( ocnt && b * FD_WG >= *ocnt ) return;           /* (a block of fd_rprod_kernel that returned at once wrote no product) */
   fe z, r;
 #pragma unroll
   for( int i=0; i<10; i++ ) z.v[i] = blk[(size_t)b*10 + i];
@@ -1874,25 +2193,31 @@ fd_rinv_kernel( u32 nblk, u32 * __restrict__ blk ) {
 __global__ void __launch_bounds__( FD_WG )
 fd_rcheck_kernel( u32 nsig, i8 * __restrict__ code, uint4 const * __restrict__ Rraw, u32 const * __restrict__ Pbuf,
                   u32 const * __restrict__ Obuf, u32 const * __restrict__ blk, u32 * __restrict__ slow,
-                  u32 * __restrict__ slow_cnt ) {
+                  u32 * __restrict__ slow_cnt,
+                  /* as fd_rprod_kernel's; rstride: uint4 of Rraw per signature (2; 4 where R's bytes lie in the
+                     signature's Rxy slot); preq: the code of a signature whose bytes differ */
+                  u32 const * __restrict__ order, u32 const * __restrict__ ocnt, u32 rstride, int preq ) {
   __shared__ u32 nslow, base;
-  u32 s = blockIdx.x * FD_WG + threadIdx.x;          /* same grid as fd_rprod_kernel: block = 256 signatures */
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;          /* same grid as fd_rprod_kernel: block = 256 signatures */
+  u32 cnt = order ? *ocnt : nsig;
+  if( blockIdx.x * FD_WG >= cnt ) return;
+  u32 s = ( order && i < cnt ) ? order[i] : i;
   if( threadIdx.x == 0u ) nslow = 0u;
   __syncthreads();
-  int c = s < nsig ? (int)code[s] : FD_ED25519_ERR_SIG;
+  int c = i < cnt ? (int)code[s] : FD_ED25519_ERR_SIG;
   int is_slow = c == FD_PEND_ASMALL;
   if( c == FD_ED25519_SUCCESS ) {
     size_t n = nsig;
     fe o, bi, zi, X, Y, x, y;
-    fe_load_planar( o, Obuf + s, n );
+    fe_load_planar( o, Obuf + i, n );
 #pragma unroll
     for( int i=0; i<10; i++ ) bi.v[i] = blk[(size_t)blockIdx.x*10 + i];
     fe_mul( zi, o, bi );
-    fe_load_planar( X, Pbuf + s, n );
-    fe_load_planar( Y, Pbuf + 10*n + s, n );
+    fe_load_planar( X, Pbuf + i, n );
+    fe_load_planar( Y, Pbuf + 10*n + i, n );
     fe_mul( x, X, zi ); fe_mul( y, Y, zi );
     u32 wx[8], wy[8]; fe_pack( wx, x ); fe_pack( wy, y );
-    uint4 r0 = Rraw[2*(size_t)s], r1 = Rraw[2*(size_t)s+1];
+    uint4 r0 = Rraw[rstride*(size_t)s], r1 = Rraw[rstride*(size_t)s+1];
     u32 rw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
     u32 diff = ( wx[0] & 1u ) ^ ( rw[7] >> 31 );      /* sign bit = parity of x */
     rw[7] &= 0x7fffffffu;
@@ -1913,22 +2238,23 @@ fd_rcheck_kernel( u32 nsig, i8 * __restrict__ code, uint4 const * __restrict__ R
      global atomic per block that has any), so fd_rslow_kernel's decodes
      fill whole waves instead of stalling every wave that holds one */
   u32 li = 0u;
-  if( is_slow ) { if( c == FD_ED25519_SUCCESS ) code[s] = FD_PEND_REQ; li = atomicAdd( &nslow, 1u ); }
+  if( is_slow ) { if( c == FD_ED25519_SUCCESS ) code[s] = (i8)preq; li = atomicAdd( &nslow, 1u ); }
   __syncthreads();
   if( threadIdx.x == 0u && nslow ) base = atomicAdd( slow_cnt, nslow );
   __syncthreads();
-  if( is_slow ) slow[ base + li ] = s;
+  if( is_slow ) slow[ base + li ] = i;
 }
 
 __global__ void __launch_bounds__( FD_WG )
 fd_rslow_kernel( u32 nsig, int semantics, i8 * __restrict__ code, uint4 const * __restrict__ Rraw,
-                 u32 const * __restrict__ Pbuf, u32 const * __restrict__ slow, u32 const * __restrict__ slow_cnt ) {
+                 u32 const * __restrict__ Pbuf, u32 const * __restrict__ slow, u32 const * __restrict__ slow_cnt,
+                 u32 const * __restrict__ order, u32 rstride ) {   /* as fd_rcheck_kernel's: the list names places */
   u32 i = blockIdx.x * FD_WG + threadIdx.x;
   if( i >= *slow_cnt ) return;
-  u32 s = slow[i];
+  u32 col = slow[i], s = order ? order[col] : col;
   int c = code[s];
   size_t n = nsig;
-  uint4 r0 = Rraw[2*(size_t)s], r1 = Rraw[2*(size_t)s+1];
+  uint4 r0 = Rraw[rstride*(size_t)s], r1 = Rraw[rstride*(size_t)s+1];
   u32 rw[8] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w };
   ge_p3 R; int rb;
   ge_decode1( R, rb, rw );
@@ -1939,9 +2265,9 @@ fd_rslow_kernel( u32 nsig, int semantics, i8 * __restrict__ code, uint4 const * 
   else if( rfail || ge_affine_is_small_order( R ) ) r = FD_ED25519_ERR_SIG;               /* (3), (5) */
   else {                                                /* (6) fd_ed25519_point_eq_z1 */
     fe X, Y, Z, u;
-    fe_load_planar( X, Pbuf + s, n );
-    fe_load_planar( Y, Pbuf + 10*n + s, n );
-    fe_load_planar( Z, Pbuf + 20*n + s, n );
+    fe_load_planar( X, Pbuf + col, n );
+    fe_load_planar( Y, Pbuf + 10*n + col, n );
+    fe_load_planar( Z, Pbuf + 20*n + col, n );
     fe_mul( u, R.X, Z ); int okx = fe_eq( u, X );
     fe_mul( u, R.Y, Z ); int oky = fe_eq( u, Y );
     r = (okx & oky) ? FD_ED25519_SUCCESS : FD_ED25519_ERR_MSG;
@@ -2138,13 +2464,14 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
                     /* KS: the signatures per key, counted at the representative up to hot_min (launch_batch zeroes
                        kcnt[0, nsig) ahead): a plain read first and a no-return add only while below the bound, so
                        one key with a million signatures does not serialise a million atomics on one word.  The
-                       bypass counts nothing: no hot keys then.  Also zeroes fd_keysplit_kernel's three counters,
-                       ucnt[3..5]. */
+                       bypass counts nothing: no hot and no fixed-base keys then.  hot_min is the largest bound a
+                       later kernel compares with (FD_FB_MIN with fixed-base keys on).  Also zeroes the counters of
+                       fd_keyclass_kernel and fd_keysplit_kernel, ucnt[3..7]. */
                     u32 *                    __restrict__ kcnt,
                     u32                                   hot_min ) {
   __shared__ u32 wcnt[ FD_WG / 64 + 1 ];
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
-  if( KS && !s ) { ucnt[3] = 0u; ucnt[4] = 0u; ucnt[5] = 0u; }
+  if( KS && !s ) { for( int k=3; k<8; k++ ) ucnt[k] = 0u; }   /* (FD_KC_*: the three of the split, two of the fixed-base keys) */
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
   int peek = !bypass;
   int own = s < nsig;
@@ -2227,33 +2554,59 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
      cnt[0..2]           hot keys, hot signatures, cold signatures (zeroed by fd_keydedup_kernel).
    A ballot per wave, the waves' counts summed in LDS, one atomic add per workgroup and list, as ulist.  No lane
    reads what another lane of this launch writes. */
+/* fidx (fixed-base keys; NULL: none): a signature whose key counted fb_min signatures and whose
+   representative fd_keyclass_kernel gave an index is fixed-base and not hot (a batch without such a key reads no
+   fidx[], and the bypass counted nothing); those fill order[] from the front (cnt[FD_KC_FB]), and the hot ones are listed
+   in orderh[] instead, because where their segment of order[] starts is known only after this launch (ks_sig). */
 __global__ void __launch_bounds__( FD_WG )
 fd_keysplit_kernel( u32 nsig, u32 const * __restrict__ arep, u32 const * __restrict__ kcnt, u32 hot_min,
                     u32 * __restrict__ hidx, u32 * __restrict__ hlist, u32 * __restrict__ order, u32 * __restrict__ cnt,
-                    u32 hcap ) {
-  __shared__ u32 wc[ 3 ][ FD_WG / 64 ], base[ 3 ];
+                    u32 hcap, u32 const * __restrict__ fidx, u32 * __restrict__ orderh, u32 fb_min ) {
+  __shared__ u32 wc[ 4 ][ FD_WG / 64 ], base[ 4 ];
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   int in = s < nsig;
   u32 rep = in ? arep[s] : 0u;
-  int hot = in && kcnt[rep] >= hot_min;
-  int f[ 3 ] = { hot && rep == s, hot, in && !hot };
-  u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, rank[ 3 ];
+  u32 kc = in ? kcnt[rep] : 0u;
+  int fb  = fidx && kc >= fb_min && fidx[rep] != FD_FB_NONE;   /* (fidx[] is read, and was written, only for such keys) */
+  int hot = !fb && kc >= hot_min;
+  int f[ 4 ] = { hot && rep == s, hot, in && !hot && !fb, fb };
+  u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, rank[ 4 ];
 #pragma unroll
-  for( int k=0; k<3; k++ ) {
+  for( int k=0; k<4; k++ ) {
     unsigned long long mk = __ballot( f[k] );
     if( !lane ) wc[k][wv] = (u32)__popcll( mk );
     rank[k] = (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) );
   }
   __syncthreads();
-  if( threadIdx.x < 3u ) {
+  if( threadIdx.x < 4u ) {
     u32 k = threadIdx.x, tot = 0u;
     for( u32 w=0; w<FD_WG/64; w++ ) { u32 c = wc[k][w]; wc[k][w] = tot; tot += c; }
-    base[k] = tot ? atomicAdd( cnt + k, tot ) : 0u;
+    base[k] = tot ? atomicAdd( cnt + ( k < 3u ? k : (u32)FD_KC_FB ), tot ) : 0u;
   }
   __syncthreads();
   if( f[0] ) { u32 i = base[0] + wc[0][wv] + rank[0]; if( i < hcap ) { hidx[s] = i; hlist[i] = s; } }
-  if( f[1] ) order[ base[1] + wc[1][wv] + rank[1] ] = s;
+  if( f[1] ) ( fidx ? orderh : order )[ base[1] + wc[1][wv] + rank[1] ] = s;
   if( f[2] ) order[ nsig - 1u - ( base[2] + wc[2][wv] + rank[2] ) ] = s;
+  if( f[3] ) order[ base[3] + wc[3][wv] + rank[3] ] = s;
+}
+
+/* Fixed-base keys, between fd_keydedup_kernel and fd_keysplit_kernel, one lane per representative
+   (ulist[0, ucnt[0]); the grid holds the worst case, blocks beyond the count return at once): one whose key has
+   fb_min signatures claims a dense index (cnt[FD_KC_FBK], one atomic add per such key: at most nsig / fb_min of
+   them) and is listed by it; an index beyond fcap leaves the key hot.  fidx[rep] = that index, or FD_FB_NONE, written
+   for these representatives alone: fd_keysplit_kernel reads it only where the count reached fb_min too.  A launch
+   of its own, because fd_keysplit_kernel's lanes read their representative's class.  A batch the de-duplication
+   only sampled (ucnt[1] set) counted nothing: no lane of this kernel does anything. */
+__global__ void __launch_bounds__( FD_WG )
+fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucnt, u32 const * __restrict__ kcnt,
+                    u32 fb_min, u32 * __restrict__ fidx, u32 * __restrict__ flist, u32 * __restrict__ cnt, u32 fcap ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( ucnt[1] || i >= ucnt[0] ) return;
+  u32 s = ulist[i];
+  if( kcnt[s] < fb_min ) return;
+  u32 fi = atomicAdd( cnt + FD_KC_FBK, 1u );
+  if( fi < fcap ) flist[fi] = s; else fi = FD_FB_NONE;
+  fidx[s] = fi;
 }
 
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
@@ -2607,6 +2960,17 @@ struct fdgpu_ed25519_ctx {
   u32 *   d_order;               /*   [max_sig] hot signatures from the front, cold from the back */
   uint4 * d_htab;                /*   [hot_cap][2][8][8] the high tables, 2 KB per hot key */
   uint4 * d_btabh;               /*   [3][FD_BTAB_ENTRIES][6] [0..32768](2^e B), e = 72, 140, 196 */
+  int     key_fixed;             /* ... and the keys with fb_min signatures get fixed-base tables: the resolved
+                                    choice, 1 = on (needs key_split), 0 = off */
+  u32     fb_min;                /*   signatures that make a key fixed-base (FD_FB_MIN; fdgpu_debug_opts_t.key_fixed = 2: 4) */
+  u32     fb_cap;                /*   min( max_sig / fb_min, FD_FB_CAP ): the most fixed-base keys of a batch */
+  u32 *   d_fidx;                /*   [max_sig] a fixed-base representative's dense index, else FD_FB_NONE */
+  u32 *   d_flist;               /*   [fb_cap] the fixed-base representatives */
+  u32 *   d_orderh;              /*   [max_sig] the hot signatures as the split lists them (ks_sig) */
+  uint4 * d_fbase;               /*   [fb_cap][8][8] [2^(32t)](-A), cached form */
+  uint4 * d_ftab;                /*   [fb_cap][8][128][6] the keys' tables, 96 KB per key */
+  uint4 * d_btabf;               /*   [8][FD_BTAB_ENTRIES][6] [0..32768]([2^(32t)]B) */
+  u32 *   d_fslow;               /*   [max_sig] the fixed-base places whose R needs its decode (fd_rslow_kernel) */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
@@ -2816,8 +3180,10 @@ enum {
   FD_SW_KEYS     = 1,   /* the distinct keys' count; from here ucnt[0..2] of fd_keydedup_kernel and fd_decode_kernel */
   FD_SW_DISTINCT = 2,   /* were most keys of the batch before distinct? */
   FD_SW_SAMPLE   = 3,   /* the count of the sample that decides it */
-  FD_SW_HOT      = 4,   /* the hot keys, then the hot and the cold signatures: fd_keysplit_kernel's three counters */
-  FD_SW_CNT      = 8 };
+  FD_SW_HOT      = 4,   /* the hot keys, then the hot and the cold signatures, the fixed-base keys claimed and the
+                           fixed-base signatures: the counters of fd_keysplit_kernel and fd_keyclass_kernel (FD_KC_*) */
+  FD_SW_FBSLOW   = 9,   /* the count of the fixed-base R check's list (d_fslow) */
+  FD_SW_CNT      = 16 };
 static u32 * slow_word( fdgpu_ed25519_ctx_t const * ctx, int w ) { return ctx->d_slow + ctx->max_sig + w; }
 
 /* What every kernel launch of one batch shares */
@@ -2867,7 +3233,8 @@ static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int la
     hipLaunchKernelGGL( fd_dsmh_kernel<0>, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                         ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, 0u,
                         ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL, (u32 const *)NULL,
-                        (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL );
+                        (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL,
+                        (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL, (u32 *)NULL );
   else                                         /* one lane, full length (no carry fold up to nofold_max) */
     hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
                         nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 0 );
@@ -2881,10 +3248,11 @@ static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int la
 /* Half-size throughput path: each distinct key decoded once (fd_keydedup_kernel), the signatures of repeated keys
    ordered ahead of the others (fd_keysplit_kernel), fd_decode_kernel (A and R with their tables), fd_hashh_kernel
    (result codes, hash, (c0, c1, s'), the hot keys' high tables), then the walk fd_dsmh_kernel with the head of the
-   slow list in its first blocks, and fd_dsm_slow_kernel for the rest. */
+   slow list in its first blocks, and fd_dsm_slow_kernel for the rest.  With fixed-base keys (kf) also
+   fd_keyclass_kernel ahead of the split, fd_ftab_kernel ahead of the walk and the R-check chain behind it. */
 static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   u32 nsig = b.nsig; unsigned sg = b.sg; i8 * code = b.code; hipStream_t st = b.st;
-  int kd = ctx->key_dedup, ks = ctx->key_split;                   /* (ks needs kd) */
+  int kd = ctx->key_dedup, ks = ctx->key_split, kf = ctx->key_fixed;   /* (ks needs kd, kf needs ks) */
   u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW ), * ucnt = slow_word( ctx, FD_SW_KEYS );
   /* kd: A's status and -A's table are the representative's.  ks: lane i <-> signature order[i], hot blocks then
      cold blocks (at most sg + 1 of them) */
@@ -2901,27 +3269,46 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
     hipLaunchKernelGGL( ( ks ? fd_keydedup_kernel<1> : fd_keydedup_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, b.d_payload,
                         b.d_desc, ctx->d_map, nsig, ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep,
                         ctx->d_ulist, ucnt, ctx->d_pstat, FD_KD_SBLK( sg ), ks ? ctx->d_kcnt : (u32 *)NULL,
-                        ks ? ctx->hot_min : 0u );
+                        kf && ctx->fb_min > ctx->hot_min ? ctx->fb_min : ks ? ctx->hot_min : 0u );
+    if( kf )
+      hipLaunchKernelGGL( fd_keyclass_kernel, dim3(sg), dim3(FD_WG), 0, st, (u32 const *)ctx->d_ulist, (u32 const *)ucnt,
+                          (u32 const *)ctx->d_kcnt, ctx->fb_min, ctx->d_fidx, ctx->d_flist, slow_word( ctx, FD_SW_HOT ),
+                          ctx->fb_cap );
     if( ks )
       hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
                           (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
-                          slow_word( ctx, FD_SW_HOT ), ctx->hot_cap );
+                          slow_word( ctx, FD_SW_HOT ), ctx->hot_cap, (u32 const *)( kf ? ctx->d_fidx : NULL ),
+                          kf ? ctx->d_orderh : (u32 *)NULL, kf ? ctx->fb_min : 0u );
   }
   /* kd: A lanes over the representatives in the first sg blocks, R lanes over every signature; else lanes 2s, 2s+1 */
-  hipLaunchKernelGGL( fd_decode_kernel, dim3( kd ? 2*sg : (unsigned)( ( 2UL*nsig + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
+  /* kf: the R lanes by place in the partition (sg + 2 blocks at most), none for the fixed-base signatures */
+  hipLaunchKernelGGL( fd_decode_kernel, dim3( kf ? 2*sg + 2 : kd ? 2*sg : (unsigned)( ( 2UL*nsig + FD_WG - 1 ) / FD_WG ) ),
+                      dim3(FD_WG), 0, st,
                       b.d_payload, b.d_desc, ctx->d_map, nsig, 1, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR,
                       kd ? (u32 const *)ctx->d_ulist : NULL, kd ? ucnt : (u32 *)NULL,
-                      kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u );
+                      kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u, kf ? order : (u32 const *)NULL,
+                      (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL );
   if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
   /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
      keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
   unsigned hb = ks ? (unsigned)( ( 2UL * ( nsig / ctx->hot_min ) + FD_WG - 1 ) / FD_WG ) : 0u;
-  hipLaunchKernelGGL( ( ks ? fd_hashh_kernel<1> : fd_hashh_kernel<0> ), dim3( ks ? hb + sg + 1 : sg ), dim3(FD_WG), 0, st,
+  /* kf: likewise the fixed-base keys' [2^(32t)](-A) in the next fbk blocks (eight lanes per key, the worst case of
+     min( nsig / fb_min, fb_cap ) keys); their entries after the hash (fd_ftab_kernel: two keys per block) */
+  unsigned long fkeys = kf ? nsig / ctx->fb_min : 0UL; if( fkeys > ctx->fb_cap ) fkeys = ctx->fb_cap;
+  unsigned fbk = (unsigned)( ( 8UL * fkeys + FD_WG - 1 ) / FD_WG );
+  hipLaunchKernelGGL( ( ks ? fd_hashh_kernel<1> : fd_hashh_kernel<0> ), dim3( ks ? hb + fbk + sg + ( kf ? 2 : 1 ) : sg ),
+                      dim3(FD_WG), 0, st,
                       b.d_payload, b.d_desc, ctx->d_map, nsig, ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR,
                       ctx->d_digB, ctx->d_slow, slow_cnt, (uint4 const *)ctx->d_khash, ctx->half_force_slow, ctx->d_htop,
-                      arep, (unsigned char const *)( kd ? ctx->d_astat : NULL ), order, kscnt,
+                      arep, (unsigned char const *)( kd ? ctx->d_astat : NULL ), ks ? ctx->d_order : (u32 *)NULL, kscnt,
                       (u32 const *)( ks ? ctx->d_hlist : NULL ), (uint4 const *)( ks ? ctx->d_Axy : NULL ),
-                      ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb );
+                      ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb, (u32 const *)( kf ? ctx->d_orderh : NULL ),
+                      (u32 const *)( kf ? ctx->d_flist : NULL ), kf ? ctx->d_fbase : (uint4 *)NULL, (u32)fbk,
+                      kf ? ctx->fb_cap : 0u, kf ? ctx->d_Rxy : (uint4 *)NULL );
+  if( fkeys )
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( fkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt, ctx->fb_cap,
+                        (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_astat, (uint4 const *)ctx->d_fbase,
+                        ctx->d_ftab );
   if( ctx->timing ) hipEventRecord( b.ev[1], st );
   /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the rest (if any) in
      fd_dsm_slow_kernel */
@@ -2929,11 +3316,26 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   int fold = nsig > ctx->nofold_max;
   hipLaunchKernelGGL( ( fold ? ( ks ? fd_dsmh_kernel<1,1> : fd_dsmh_kernel<1,0> )
                              : ( ks ? fd_dsmh_kernel<0,1> : fd_dsmh_kernel<0,0> ) ),
-                      dim3( nsb + sg + ( ks ? 1u : 0u ) ), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
+                      dim3( nsb + sg + ( kf ? 2u : ks ? 1u : 0u ) ), dim3(FD_WG), 0, st, nsig, ctx->d_tab, ctx->d_tabR, ctx->d_digA,
                       ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, nsb,
                       ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep, order, kscnt, hidx,
-                      (uint4 const *)( ks ? ctx->d_htab : NULL ), (uint4 const *)( ks ? ctx->d_btabh : NULL ) );
+                      (uint4 const *)( ks ? ctx->d_htab : NULL ), (uint4 const *)( ks ? ctx->d_btabh : NULL ),
+                      (u32 const *)( kf ? ctx->d_fidx : NULL ), (uint4 const *)( kf ? ctx->d_ftab : NULL ),
+                      (uint4 const *)( kf ? ctx->d_btabf : NULL ), kf ? ctx->d_P : (u32 *)NULL );
   if( ctx->timing ) hipEventRecord( b.ev[2], st );
+  if( fkeys ) {
+    /* the fixed-base signatures' R, compared undecoded: the full-length path's chain over the fixed-base segment of
+       order[] (the worst case of blocks; those beyond the device-side count return at once), with a list and a
+       counter of its own -- fd_dsm_slow_kernel below still reads the half-size slow list's */
+    u32 const * fcnt = kscnt + FD_KC_FB; u32 * fslow_cnt = slow_word( ctx, FD_SW_FBSLOW );
+    hipLaunchKernelGGL( fd_rprod_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_P, ctx->d_O, ctx->d_blk, fslow_cnt,
+                        order, fcnt );
+    hipLaunchKernelGGL( fd_rinv_kernel, dim3((sg + FD_WG - 1)/FD_WG), dim3(FD_WG), 0, st, sg, ctx->d_blk, fcnt );
+    hipLaunchKernelGGL( fd_rcheck_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_Rxy, ctx->d_P, ctx->d_O, ctx->d_blk,
+                        ctx->d_fslow, fslow_cnt, order, fcnt, 4u, FD_PEND_FBREQ );
+    hipLaunchKernelGGL( fd_rslow_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, code, ctx->d_Rxy, ctx->d_P,
+                        ctx->d_fslow, fslow_cnt, order, 4u );
+  }
   hipLaunchKernelGGL( ( fold ? fd_dsm_slow_kernel<1> : fd_dsm_slow_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, nsig,
                       ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_slow, slow_cnt,
                       nsb * FD_WG, arep, order );
@@ -2948,7 +3350,7 @@ static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW );
   hipLaunchKernelGGL( fd_decode_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig, 0,
                       ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
-                      (u32 *)NULL, (unsigned char *)NULL, 0u );
+                      (u32 *)NULL, (unsigned char *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL );
   hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig,
                       ctx->semantics, 1, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
                       (uint4 const *)ctx->d_khash );
@@ -2959,12 +3361,13 @@ static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
                       nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 1 );
   if( ctx->timing ) hipEventRecord( b.ev[2], st );
-  hipLaunchKernelGGL( fd_rprod_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_P, ctx->d_O, ctx->d_blk, slow_cnt );
-  hipLaunchKernelGGL( fd_rinv_kernel, dim3((sg + FD_WG - 1)/FD_WG), dim3(FD_WG), 0, st, sg, ctx->d_blk );
+  hipLaunchKernelGGL( fd_rprod_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_P, ctx->d_O, ctx->d_blk, slow_cnt,
+                      (u32 const *)NULL, (u32 const *)NULL );
+  hipLaunchKernelGGL( fd_rinv_kernel, dim3((sg + FD_WG - 1)/FD_WG), dim3(FD_WG), 0, st, sg, ctx->d_blk, (u32 const *)NULL );
   hipLaunchKernelGGL( fd_rcheck_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, code, ctx->d_Rxy, ctx->d_P, ctx->d_O, ctx->d_blk,
-                      ctx->d_slow, slow_cnt );
+                      ctx->d_slow, slow_cnt, (u32 const *)NULL, (u32 const *)NULL, 2u, FD_PEND_REQ );
   hipLaunchKernelGGL( fd_rslow_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, ctx->semantics, code, ctx->d_Rxy, ctx->d_P,
-                      ctx->d_slow, slow_cnt );
+                      ctx->d_slow, slow_cnt, (u32 const *)NULL, 2u );
   return 0;
 }
 
@@ -2997,14 +3400,14 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
 fdgpu_debug_set_opts( fdgpu_debug_opts_t const * opts ) {
   std::lock_guard<std::mutex> lk( g_dbg_mu );
   if( opts ) g_dbg = *opts;
-  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0 };
+  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 }
 
 /* staging + device buffers of async slot i (once) */
@@ -3102,6 +3505,23 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
         HIPCHK( ctx_dev_alloc( ctx, &ctx->d_order, ns * sizeof(u32) ), -1 );
         HIPCHK( ctx_dev_alloc( ctx, &ctx->d_htab, hc * 2 * FD_ATAB_STORED * 8 * sizeof(uint4) ), -1 );
         HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabh, (size_t)3 * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+        /* the keys with many signatures get fixed-base tables (fd_keyclass_kernel) */
+        /* (not under half_force_slow: that hook sends signatures down the half-size slow list, which a fixed-base
+           signature never sees) */
+        ctx->key_fixed = dbg.key_fixed != 1 && !ctx->half_force_slow;
+        if( ctx->key_fixed ) {
+          ctx->fb_min = dbg.key_fixed == 2 ? 4u : FD_FB_MIN;
+          unsigned long fc = ns / ctx->fb_min;
+          ctx->fb_cap = (u32)( fc < FD_FB_CAP ? fc : FD_FB_CAP );
+          size_t fcn = ctx->fb_cap ? ctx->fb_cap : 1UL;
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fidx, ns * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_flist, fcn * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_orderh, ns * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fbase, fcn * FD_FB_T * 8 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ftab, fcn * FD_FB_T * FD_FB_E * 6 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabf, (size_t)FD_FB_T * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fslow, ns * sizeof(u32) ), -1 );
+        }
       }
     }
   }
@@ -3125,6 +3545,10 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
       hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream,
                           ctx->d_btabh + (size_t)t * FD_BTAB_ENTRIES * 6, e[t] );
   }
+  if( ctx->key_fixed )
+    for( int t=0; t<FD_FB_T; t++ )
+      hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream,
+                          ctx->d_btabf + (size_t)t * FD_BTAB_ENTRIES * 6, 32*t );
   HIPCHK( hipGetLastError(), -1 );
   for( int i=0; i<FD_NSLOT; i++ ) HIPCHK( hipEventCreateWithFlags( &ctx->slot[i].done, hipEventDisableTiming ), -1 );
   HIPCHK( ctx_pin_alloc( ctx, &ctx->h_flag, ( FD_NSLOT + 2 ) * sizeof(unsigned long), &ctx->d_flag ), -1 );
@@ -4604,10 +5028,26 @@ fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, un
   if( hot_sigs ) *hot_sigs = 0UL;
   if( !ctx || !ctx->half || !ctx->key_split || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
   if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
-  u32 cnt[ 2 ] = { 0u, 0u };
+  u32 cnt[ 5 ] = { 0u, 0u, 0u, 0u, 0u };
   if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ), sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  /* the repeated keys, whichever walk they took: a fixed-base key (fdgpu_ed25519_fixed_count) is one of them */
+  if( ctx->key_fixed ) { cnt[0] += cnt[FD_KC_FBK] < ctx->fb_cap ? cnt[FD_KC_FBK] : ctx->fb_cap; cnt[1] += cnt[FD_KC_FB]; }
   if( hot_keys ) *hot_keys = (unsigned long)cnt[0];
   if( hot_sigs ) *hot_sigs = (unsigned long)cnt[1];
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys, unsigned long * fixed_sigs ) {
+  if( fixed_keys ) *fixed_keys = 0UL;
+  if( fixed_sigs ) *fixed_sigs = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_fixed || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 2 ] = { 0u, 0u };
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_FBK, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( cnt[0] > ctx->fb_cap ) cnt[0] = ctx->fb_cap;     /* (keys that claimed an index beyond the cap stayed hot) */
+  if( fixed_keys ) *fixed_keys = (unsigned long)cnt[0];
+  if( fixed_sigs ) *fixed_sigs = (unsigned long)cnt[1];
   return 0;
 }
 

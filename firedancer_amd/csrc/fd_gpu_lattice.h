@@ -374,3 +374,17 @@ FD_LAT_FN int fd_lat_skew( uint32_t c0[ 7 ], uint32_t c1m[ 5 ], int * c1neg, int
   /* (best <= FD_LAT_SKEW_NW: c0 < 2^(4 (2W + NW) - 1) = 2^215, so cr[7] = 0, and |c1| < 2^79) */
   return (int)( c1m[0] & 1u ) & ( cr[7] == 0u );
 }
+
+/* Fixed-base keys: k as 32 signed radix-256 digits, k = sum d[j] 2^(8 j) + 2^256 c with c the return value,
+   every d[j] in [-128, 128): byte j plus the carry of the digit below, minus 256 when that is 128 or more.  For
+   k < 2^255 - 2^248, and so for every k < l (top byte at most 0x10), the return value is 0. */
+FD_LAT_FN int fd_fb_recode( signed char d[ 32 ], uint32_t const k[ 8 ] ) {
+  int carry = 0;
+#pragma unroll
+  for( int j=0; j<32; j++ ) {
+    int v = (int)( ( k[ j >> 2 ] >> ( 8*( j & 3 ) ) ) & 255u ) + carry;
+    carry = ( v + 128 ) >> 8;
+    d[j] = (signed char)( v - ( carry << 8 ) );
+  }
+  return carry;
+}

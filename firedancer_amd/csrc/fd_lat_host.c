@@ -22,3 +22,9 @@ fd_lat_skew_host_many( unsigned long n, uint32_t const * k, uint32_t * c0, uint3
     ok[i] = fd_lat_skew( c0 + 7UL*i, c1m + 5UL*i, neg + i, nwin + i, k + 8UL*i );
   }
 }
+
+/* the fixed-base walk's digits of k (tests/test_fb_recode.py) */
+int
+fd_fb_recode_host( signed char d[ 32 ], uint32_t const k[ 8 ] ) {
+  return fd_fb_recode( d, k );
+}

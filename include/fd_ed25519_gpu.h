@@ -394,12 +394,24 @@ fdgpu_ed25519_key_count( fdgpu_ed25519_ctx_t * ctx );
 
 /* Repeated keys of the last batch launched on ctx: the public keys with at
    least FD_HOT_MIN (8) signatures in it, and the signatures of those keys,
-   which walk 64 doublings instead of 128 (either pointer may be NULL).
+   which walk 64 doublings instead of 128, or 24 where the key got
+   fixed-base tables (fdgpu_ed25519_fixed_count: those keys and signatures
+   are included here) (either pointer may be NULL).
    Both 0 when that batch took another path, was not de-duplicated in
    full, or the split is off (fdgpu_debug_opts_t.key_split).  Waits for
    the batch; 0 on success. */
 int
 fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, unsigned long * hot_sigs );
+
+/* Fixed-base keys of the last batch launched on ctx: the public keys with
+   at least FD_FB_MIN (128) signatures in it that got tables of their own
+   (at most 4,096 and at most max_sig / FD_FB_MIN per batch; a key beyond
+   that stays hot), and the signatures of those keys, which walk 24
+   doublings.  Both 0 when that batch took
+   another path, was not de-duplicated in full, or the tables are off
+   (fdgpu_debug_opts_t.key_fixed).  Waits for the batch; 0 on success. */
+int
+fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys, unsigned long * fixed_sigs );
 
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
@@ -750,6 +762,12 @@ typedef struct fdgpu_debug_opts {
                                         key with at least 8 signatures in the batch walk 64 doublings (fd_keysplit_kernel);
                                         1 = off (A/B: exactly the kernels and launches without it); 2 = TESTS, a key is
                                         repeated from 2 signatures on */
+  int           key_fixed;           /* half-size throughput path with key_split on: 0 = default, a key with at least 128
+                                        signatures in the batch gets fixed-base tables and its signatures walk 24
+                                        doublings, R compared undecoded (fd_keyclass_kernel, fd_ftab_kernel); 1 = off
+                                        (A/B: exactly the kernels and launches without it); 2 = TESTS, fixed-base from
+                                        4 signatures on.  Off whenever half_force_slow is set: a fixed-base signature
+                                        has no half-size scalars and so never reaches that list */
 } fdgpu_debug_opts_t;
 
 void

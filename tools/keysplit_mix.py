@@ -97,7 +97,7 @@ def main():
     for name, mode in (("on", 0), ("off", 1)):
         if name not in a.modes.split(","):
             continue
-        engine.debug_set_opts(key_split=mode)
+        engine.debug_set_opts(key_split=mode, key_fixed=1)   # (the fixed-base keys of DESIGN 16 off: tools/keyfixed_mix.py)
         try:
             eng[name] = fa.Engine(device=0, max_txn=n, max_sig=n)
         finally:
