@@ -242,6 +242,14 @@ FD_DEV u32 ks_sig( u32 const * __restrict__ order, u32 const * __restrict__ orde
 #define FD_KC_COLD 2
 #define FD_KC_FBK  3
 #define FD_KC_FB   4
+/* ... and, past the word of the fixed-base R check's list (FD_SW_FBSLOW), the key cache's: the fixed-base
+   keys of the batch found resident, those not found (the miss list's count), those that claimed a slot and build
+   their tables in this batch; where the hand stood when the batch began, and the hand, which outlives the batch */
+#define FD_KC_HIT   6
+#define FD_KC_MISS  7
+#define FD_KC_BUILD 8
+#define FD_KC_HAND0 9
+#define FD_KC_HAND  10
 
 /* ------------------------------------------------------------------ */
 
@@ -343,7 +351,16 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
                      fixed-base signature (its R is compared undecoded); NULL: one R lane per signature */
                   u32 const *              __restrict__ order,
                   u32 const *              __restrict__ orderh,
-                  u32 const *              __restrict__ kscnt ) {
+                  u32 const *              __restrict__ kscnt,
+                  /* ... and a representative whose key the context's cache held decodes nothing:
+                     fidx[] names its slot, and the slot was not claimed in this batch (birth[] != batch).  Its
+                     status is in astat[] already (fd_keyclass_kernel), and nothing reads its point or its -A table:
+                     every signature of a fixed-base key takes the fixed-base walk */
+                  u32 const *              __restrict__ kcnt,
+                  u32                                   fb_min,
+                  u32 const *              __restrict__ fidx,
+                  u32 const *              __restrict__ birth,
+                  u32                                   batch ) {
   u32 s, is_r;
   unsigned char * st;
   if( ulist ) {
@@ -363,6 +380,10 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
       }
       if( i >= cnt ) return;
       s = ulist[i]; is_r = 0u; st = astat + s;
+      if( fidx && kcnt[s] >= fb_min ) {
+        u32 slot = fidx[s];
+        if( slot != FD_FB_NONE && birth[slot] != batch ) return;
+      }
     } else if( order ) {
       u32 col, j; int cls;
       if( !ks_pos( blockIdx.x - ublk, nsig, kscnt[FD_KC_FB], kscnt[FD_KC_HOT], col, j, cls ) || cls==2 ) return;
@@ -924,13 +945,14 @@ FD_DEV void ftab_pass2( fe & inv, uint4 * __restrict__ ent, fe const (&pf)[ 8 ] 
    of fixed-base keys return at once; a key that does not decode or has small order has no table (its
    signatures' codes are final or parked before any walk). */
 __global__ void __launch_bounds__( FD_WG, 2 )          /* (two waves per SIMD asked for: the eight prefix products are 80 VGPRs) */
-fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 fcap, u32 const * __restrict__ flist,
+fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 const * __restrict__ flist,
                 unsigned char const * __restrict__ astat, uint4 const * __restrict__ fbase, uint4 * __restrict__ ftab ) {
-  u32 nk = kscnt[FD_KC_FBK]; nk = nk < fcap ? nk : fcap;
-  u32 fi = blockIdx.x * 2u + ( threadIdx.x >> 7 );
+  u32 nk = kscnt[FD_KC_BUILD];                            /* the keys that claimed a slot in this batch */
+  u32 bi = blockIdx.x * 2u + ( threadIdx.x >> 7 );
   if( blockIdx.x * 2u >= nk ) return;                     /* (block-uniform) */
   /* a wave is of one key: lanes of a key that is beyond the count, or has no table, skip the work together */
-  if( fi >= nk || ( astat[ flist[fi] ] & 7u ) ) return;
+  if( bi >= nk || ( astat[ flist[2u*bi+1u] ] & 7u ) ) return;
+  u32 fi = flist[2u*bi];                                  /* its slot */
   u32 t = ( threadIdx.x >> 4 ) & 7u, g = threadIdx.x & 15u;
   int lane = (int)( threadIdx.x & 63u );
   ge_cached pc;
@@ -1006,10 +1028,10 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  u32                                   hblk,     /* blocks [0,hblk) build them: one lane per (key, part) */
                  /* fixed-base keys (orderh = NULL: none): */
                  u32 const *              __restrict__ orderh,   /* the hot signatures as the split listed them */
-                 u32 const *              __restrict__ flist,    /* the fixed-base keys' representatives */
-                 uint4 *                  __restrict__ fbase,    /* [key][8] [2^(32t)](-A) */
+                 u32 const *              __restrict__ flist,    /* (slot, representative) of the keys claimed in this batch */
+                 uint4 *                  __restrict__ fbase,    /* [slot][8] [2^(32t)](-A) */
                  u32                                   fblk,     /* blocks [hblk,hblk+fblk) build them: one lane per (key, t) */
-                 u32                                   fcap,
+                 unsigned char *          __restrict__ sstat,    /* [slot] the key's decode status */
                  uint4 *                  __restrict__ Rraw ) {
   if( KS ) {
     if( blockIdx.x < hblk ) {
@@ -1025,11 +1047,13 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
     if( blockIdx.x < hblk + fblk ) {
       /* likewise the fixed-base keys' chains of 32 t doublings, ahead of fd_ftab_kernel */
       u32 i = ( blockIdx.x - hblk ) * FD_WG + threadIdx.x;
-      u32 nk = kscnt[FD_KC_FBK]; nk = nk < fcap ? nk : fcap;
-      if( ( i >> 3 ) >= nk ) return;
-      u32 rep = flist[ i >> 3 ];
+      /* (of the keys that claimed a slot in this batch, by slot; the slot records the key's status,
+         whether or not it decodes, for the batches that find it resident) */
+      if( ( i >> 3 ) >= kscnt[FD_KC_BUILD] ) return;
+      u32 slot = flist[ 2u*( i >> 3 ) ], rep = flist[ 2u*( i >> 3 ) + 1u ];
+      if( !( i & 7u ) ) sstat[slot] = astat[rep];
       if( astat[rep] & 7u ) return;
-      fbase_build( fbase, i >> 3, i & 7u, Axy, rep );
+      fbase_build( fbase, slot, i & 7u, Axy, rep );
       return;
     }
     u32 col, j; int cls;
@@ -2446,6 +2470,35 @@ FD_DEV u64 fd_xxh64_64( u64 seed, unsigned char const * p ) {
    Which of a key's signatures wins its slot differs from run to run; every one of them gives the same
    point, status and table. */
 #define FD_KD_PROBES 16u
+/* a key's hash: XXH64's rounds over its four 64-bit words, seeded per batch */
+FD_DEV u64 fd_key_hash( u32 const w[ 8 ], u32 seed32 ) {
+  u64 seed = (u64)seed32 * FD_XXP3;
+  u64 v0 = fd_xxh_round( seed + FD_XXP1 + FD_XXP2, ((u64)w[1] << 32) | (u64)w[0] );
+  u64 v1 = fd_xxh_round( seed + FD_XXP2,           ((u64)w[3] << 32) | (u64)w[2] );
+  u64 v2 = fd_xxh_round( seed,                     ((u64)w[5] << 32) | (u64)w[4] );
+  u64 v3 = fd_xxh_round( seed - FD_XXP1,           ((u64)w[7] << 32) | (u64)w[6] );
+  u64 h = fd_rotl64( v0, 1 ) + fd_rotl64( v1, 7 ) + fd_rotl64( v2, 12 ) + fd_rotl64( v3, 18 );
+  h ^= h >> 33; h *= FD_XXP2; h ^= h >> 29; h *= FD_XXP3; h ^= h >> 32;
+  return h;
+}
+
+/* The key cache: a context keeps the tables of its fixed-base keys from batch to batch.  Slot i of
+   fb_cap holds a key's 32 bytes (key[8 i]), a state word (0 = empty, else the number of the batch that last used
+   the slot), the number of the batch that claimed it (birth: the batch that builds its tables), the key's decode
+   status (stat), and row i of fbase[] and ftab[].  A context's batches are serial on one stream, so a batch reads
+   what the batch before left and nothing else moves under it. */
+struct fd_kcache {
+  u32 *           key;
+  u32 *           state;
+  u32 *           birth;
+  unsigned char * stat;
+  u32 *           idx;       /* this batch's index of the resident keys: 0 = empty, else 1 + slot; imask + 1 words, cleared
+                                with ktab by launch_half's memset, filled by the front blocks of fd_keydedup_kernel */
+  u32             imask, iprobes;
+  u32             fcap;      /* slots */
+  u32             batch;     /* this batch's number, never 0 */
+};
+
 template<int KS>
 __global__ void __launch_bounds__( FD_WG )
 fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
@@ -2468,10 +2521,32 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
                        later kernel compares with (FD_FB_MIN with fixed-base keys on).  Also zeroes the counters of
                        fd_keyclass_kernel and fd_keysplit_kernel, ucnt[3..7]. */
                     u32 *                    __restrict__ kcnt,
-                    u32                                   hot_min ) {
+                    u32                                   hot_min,
+                    /* the key cache (KS, fixed-base keys on; else iblk = 0): the first iblk blocks index the resident
+                       keys, one lane per slot -- a slot that finds no place within the probes cannot be found in
+                       this batch, and its key is then a miss, which costs a build and nothing else */
+                    u32                                   iblk,
+                    fd_kcache                             kc ) {
   __shared__ u32 wcnt[ FD_WG / 64 + 1 ];
-  u32 s = blockIdx.x * FD_WG + threadIdx.x;
-  if( KS && !s ) { for( int k=3; k<8; k++ ) ucnt[k] = 0u; }   /* (FD_KC_*: the three of the split, two of the fixed-base keys) */
+  if( KS && blockIdx.x < iblk ) {
+    u32 slot = blockIdx.x * FD_WG + threadIdx.x;
+    if( slot >= kc.fcap || !kc.state[slot] ) return;
+    u32 w[8];
+#pragma unroll
+    for( int k=0; k<8; k++ ) w[k] = kc.key[ 8u*slot + k ];
+    u32 h = (u32)( fd_key_hash( w, seed32 ) >> 32 );
+    for( u32 i=0; i<kc.iprobes; i++ )
+      if( !atomicCAS( kc.idx + ( ( h + i ) & kc.imask ), 0u, slot + 1u ) ) break;
+    return;
+  }
+  u32 bx = KS ? blockIdx.x - iblk : blockIdx.x;
+  u32 s = bx * FD_WG + threadIdx.x;
+  if( KS && !s ) {
+    u32 * c = ucnt + 3;                                       /* (FD_KC_*: the three of the split, two of the fixed-base keys, */
+    for( int k=0; k<5; k++ ) c[k] = 0u;                       /*  three of the key cache; the hand brought back below the slots */
+    for( int k=FD_KC_HIT; k<=FD_KC_BUILD; k++ ) c[k] = 0u;    /*  so that a batch's draws never wrap, and its start noted) */
+    if( iblk ) { u32 h = c[FD_KC_HAND] % kc.fcap; c[FD_KC_HAND] = h; c[FD_KC_HAND0] = h; }
+  }
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
   int peek = !bypass;
   int own = s < nsig;
@@ -2480,16 +2555,10 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
     pstat[2u*s] = 0u;
     u32 m = map[s];
     fdgpu_txn_desc_t d = desc[m & 0xffffffu];
-    if( ( !bypass || blockIdx.x < sblk ) && txn_desc_ok( d ) ) {
+    if( ( !bypass || bx < sblk ) && txn_desc_ok( d ) ) {
       u32 w[8];
       fd_load_words<8>( w, payload + d.payload_off + (u32)d.acct_addr_off + 32u*( m >> 24 ) );
-      u64 seed = (u64)seed32 * FD_XXP3;
-      u64 v0 = fd_xxh_round( seed + FD_XXP1 + FD_XXP2, ((u64)w[1] << 32) | (u64)w[0] );
-      u64 v1 = fd_xxh_round( seed + FD_XXP2,           ((u64)w[3] << 32) | (u64)w[2] );
-      u64 v2 = fd_xxh_round( seed,                     ((u64)w[5] << 32) | (u64)w[4] );
-      u64 v3 = fd_xxh_round( seed - FD_XXP1,           ((u64)w[7] << 32) | (u64)w[6] );
-      u64 h = fd_rotl64( v0, 1 ) + fd_rotl64( v1, 7 ) + fd_rotl64( v2, 12 ) + fd_rotl64( v3, 18 );
-      h ^= h >> 33; h *= FD_XXP2; h ^= h >> 29; h *= FD_XXP3; h ^= h >> 32;
+      u64 h = fd_key_hash( w, seed32 );
       for( u32 i=0; i<probes; i++ ) {
         u32 * slot = ktab + ( ( (u32)h + i ) & kmask );
         u32 v = peek ? __hip_atomic_load( slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP ) : 0u;   /* an ordinary load */
@@ -2530,16 +2599,16 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
     u32 base = 0u;
     if( !bypass ) {
       if( tot ) base = atomicAdd( ucnt, tot );
-      if( tot && blockIdx.x < sblk ) atomicAdd( ucnt + 2, tot );     /* the sample's representatives */
-    } else if( blockIdx.x < sblk ) {
+      if( tot && bx < sblk ) atomicAdd( ucnt + 2, tot );     /* the sample's representatives */
+    } else if( bx < sblk ) {
       if( tot ) { base = ( nsig - nsamp ) + atomicAdd( ucnt + 2, tot ); atomicAdd( ucnt, tot ); }
-      if( !blockIdx.x && nsig > nsamp ) atomicAdd( ucnt, nsig - nsamp );
+      if( !bx && nsig > nsamp ) atomicAdd( ucnt, nsig - nsamp );
     }
     wcnt[ FD_WG/64 ] = base;
   }
   __syncthreads();
   if( own ) {
-    if( bypass && blockIdx.x >= sblk ) ulist[ s - nsamp ] = s;
+    if( bypass && bx >= sblk ) ulist[ s - nsamp ] = s;
     else ulist[ wcnt[ FD_WG/64 ] + wcnt[wv] + (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) ) ] = s;
   }
 }
@@ -2590,23 +2659,84 @@ fd_keysplit_kernel( u32 nsig, u32 const * __restrict__ arep, u32 const * __restr
   if( f[3] ) order[ base[3] + wc[3][wv] + rank[3] ] = s;
 }
 
-/* Fixed-base keys (DESIGN 16), between fd_keydedup_kernel and fd_keysplit_kernel, one lane per representative
+/* Fixed-base keys (DESIGN 16, 17), between fd_keydedup_kernel and fd_keysplit_kernel, one lane per representative
    (ulist[0, ucnt[0]); the grid holds the worst case, blocks beyond the count return at once): one whose key has
-   fb_min signatures claims a dense index (cnt[FD_KC_FBK], one atomic add per such key: at most nsig / fb_min of
-   them) and is listed by it; an index beyond fcap leaves the key hot.  fidx[rep] = that index, or FD_FB_NONE, written
-   for these representatives alone: fd_keysplit_kernel reads it only where the count reached fb_min too.  A launch
-   of its own, because fd_keysplit_kernel's lanes read their representative's class.  A batch the de-duplication
-   only sampled (ucnt[1] set) counted nothing: no lane of this kernel does anything. */
+   fb_min signatures looks the key up among the context's resident keys (the index the launch before filled; all
+   32 bytes compared, a hash match alone never counts).
+     hit   the slot is stamped with this batch's number (a plain store: every writer writes the same value), which
+           keeps it from this batch's claims; fidx[rep] = the slot, astat[rep] = the status the slot recorded --
+           fd_decode_kernel skips this representative -- and cnt[FD_KC_FBK], cnt[FD_KC_HIT] count it;
+     miss  fidx[rep] = FD_FB_NONE, and the representative joins mlist[] (one atomic add per miss: at most
+           nsig / fb_min of them) for fd_keyclaim_kernel.
+   fidx[rep] is written for these representatives alone: fd_keysplit_kernel reads it only where the count reached
+   fb_min too.  A launch of its own, because fd_keysplit_kernel's lanes read their representative's class.  A
+   batch the de-duplication only sampled (ucnt[1] set) counted nothing: no lane of this kernel does anything. */
 __global__ void __launch_bounds__( FD_WG )
 fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucnt, u32 const * __restrict__ kcnt,
-                    u32 fb_min, u32 * __restrict__ fidx, u32 * __restrict__ flist, u32 * __restrict__ cnt, u32 fcap ) {
+                    u32 fb_min, u32 * __restrict__ fidx, u32 * __restrict__ mlist, u32 * __restrict__ cnt,
+                    unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
+                    u32 const * __restrict__ map, u32 seed32, unsigned char * __restrict__ astat, fd_kcache kc ) {
   u32 i = blockIdx.x * FD_WG + threadIdx.x;
   if( ucnt[1] || i >= ucnt[0] ) return;
   u32 s = ulist[i];
   if( kcnt[s] < fb_min ) return;
-  u32 fi = atomicAdd( cnt + FD_KC_FBK, 1u );
-  if( fi < fcap ) flist[fi] = s; else fi = FD_FB_NONE;
-  fidx[s] = fi;
+  u32 m = map[s];
+  fdgpu_txn_desc_t d = desc[m & 0xffffffu];
+  u32 w[8];
+  fd_load_words<8>( w, payload + d.payload_off + (u32)d.acct_addr_off + 32u*( m >> 24 ) );
+  u32 h = (u32)( fd_key_hash( w, seed32 ) >> 32 );
+  for( u32 p=0; p<kc.iprobes; p++ ) {
+    u32 v = kc.idx[ ( h + p ) & kc.imask ];
+    if( !v ) break;                                  /* (no insert after the launch before: an empty word ends the search) */
+    u32 slot = v - 1u;
+    if( slot >= kc.fcap ) continue;
+    u32 diff = 0u;
+#pragma unroll
+    for( int k=0; k<8; k++ ) diff |= w[k] ^ kc.key[ 8u*slot + k ];
+    if( diff ) continue;
+    kc.state[slot] = kc.batch;
+    fidx[s] = slot;
+    astat[s] = kc.stat[slot];
+    atomicAdd( cnt + FD_KC_FBK, 1u ); atomicAdd( cnt + FD_KC_HIT, 1u );
+    return;
+  }
+  fidx[s] = FD_FB_NONE;
+  mlist[ atomicAdd( cnt + FD_KC_MISS, 1u ) ] = s;
+}
+
+/* The misses claim slots, one lane per miss; the grid holds min( nsig / fb_min, fb_cap ) lanes, blocks
+   beyond the device-side count return at once, and with more misses than slots the first fb_cap of the list try.  A
+   lane draws slot numbers from the hand -- atomicAdd( hand, 1 ) % fb_cap, the hand below fb_cap when the batch began
+   -- and takes the first slot whose state word is not this batch's number, until the batch's draws have gone
+   round all fb_cap slots.  Every hand value goes to exactly one lane and names, within a batch, a slot of its own,
+   and every hit was stamped by the launch before: no claim races with a hit or with another claim, and nothing
+   is compared and swapped.  The claimant writes the key, both stamps and fidx[rep], and lists (slot, rep) for
+   fbase_build and fd_ftab_kernel.  A miss that finds no slot keeps FD_FB_NONE and stays hot. */
+__global__ void __launch_bounds__( FD_WG )
+fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 * __restrict__ fidx,
+                    u32 * __restrict__ flist, unsigned char const * __restrict__ payload,
+                    fdgpu_txn_desc_t const * __restrict__ desc, u32 const * __restrict__ map, fd_kcache kc ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i >= cnt[FD_KC_MISS] || i >= kc.fcap ) return;
+  u32 s = mlist[i], hand0 = cnt[FD_KC_HAND0];
+  for(;;) {
+    u32 hv = atomicAdd( cnt + FD_KC_HAND, 1u );
+    if( hv - hand0 >= kc.fcap ) return;
+    u32 slot = hv % kc.fcap;
+    if( kc.state[slot] == kc.batch ) continue;       /* a hit of this batch (claims of it are at other hand values) */
+    u32 m = map[s];
+    fdgpu_txn_desc_t d = desc[m & 0xffffffu];
+    u32 w[8];
+    fd_load_words<8>( w, payload + d.payload_off + (u32)d.acct_addr_off + 32u*( m >> 24 ) );
+#pragma unroll
+    for( int k=0; k<8; k++ ) kc.key[ 8u*slot + k ] = w[k];
+    kc.state[slot] = kc.batch; kc.birth[slot] = kc.batch;
+    fidx[s] = slot;
+    u32 b = atomicAdd( cnt + FD_KC_BUILD, 1u );
+    flist[2u*b] = slot; flist[2u*b+1u] = s;
+    atomicAdd( cnt + FD_KC_FBK, 1u );
+    return;
+  }
 }
 
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
@@ -2964,8 +3094,21 @@ struct fdgpu_ed25519_ctx {
                                     choice, 1 = on (needs key_split), 0 = off */
   u32     fb_min;                /*   signatures that make a key fixed-base (FD_FB_MIN; fdgpu_debug_opts_t.key_fixed = 2: 4) */
   u32     fb_cap;                /*   min( max_sig / fb_min, FD_FB_CAP ): the most fixed-base keys of a batch */
-  u32 *   d_fidx;                /*   [max_sig] a fixed-base representative's dense index, else FD_FB_NONE */
-  u32 *   d_flist;               /*   [fb_cap] the fixed-base representatives */
+  u32 *   d_fidx;                /*   [max_sig] a fixed-base representative's slot, else FD_FB_NONE */
+  u32 *   d_flist;               /*   [fb_cap][2] (slot, representative) of the keys that claimed a slot in this batch */
+  /* the key cache: fb_cap slots that keep a key's fbase row and tables from batch to batch.  The
+     context's batches are serial on one stream (its work buffers are shared), which is what makes this safe. */
+  int     kc_mode;               /*   fdgpu_debug_opts_t.key_cache: 0 on, 1 off (every batch starts empty), 2 tests */
+  int     kc_dirty;              /*   a launch failed: the next batch clears every slot first */
+  u32     kc_batch;              /*   the batch number: one more per launch_half call, never 0 */
+  u32     kc_iwords, kc_iprobes; /*   the per-batch index: words (a power of two, >= 4 fb_cap) in front of d_ktab; probes */
+  u32 *   d_kidx;                /*   [kc_iwords] the index, then d_ktab: one memset clears both */
+  u32 *   d_skey;                /*   [fb_cap][8] a slot's key */
+  u32 *   d_sstate;              /*   [fb_cap] 0 = empty, else the batch that last used the slot; then [fb_cap] the batch that
+                                      claimed it (d_sbirth) */
+  u32 *   d_sbirth;
+  unsigned char * d_sstat;       /*   [fb_cap] the key's decode status */
+  u32 *   d_mlist;               /*   [max_sig / fb_min + 1] the representatives of this batch's misses */
   u32 *   d_orderh;              /*   [max_sig] the hot signatures as the split lists them (ks_sig) */
   uint4 * d_fbase;               /*   [fb_cap][8][8] [2^(32t)](-A), cached form */
   uint4 * d_ftab;                /*   [fb_cap][8][128][6] the keys' tables, 96 KB per key */
@@ -3183,6 +3326,8 @@ enum {
   FD_SW_HOT      = 4,   /* the hot keys, then the hot and the cold signatures, the fixed-base keys claimed and the
                            fixed-base signatures: the counters of fd_keysplit_kernel and fd_keyclass_kernel (FD_KC_*) */
   FD_SW_FBSLOW   = 9,   /* the count of the fixed-base R check's list (d_fslow) */
+  FD_SW_KCACHE   = 10,  /* the key cache's hits, misses and builds, the hand's start and the hand (FD_KC_HIT.., counted from
+                           FD_SW_HOT); the hand alone outlives a batch */
   FD_SW_CNT      = 16 };
 static u32 * slow_word( fdgpu_ed25519_ctx_t const * ctx, int w ) { return ctx->d_slow + ctx->max_sig + w; }
 
@@ -3249,7 +3394,9 @@ static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int la
    ordered ahead of the others (fd_keysplit_kernel), fd_decode_kernel (A and R with their tables), fd_hashh_kernel
    (result codes, hash, (c0, c1, s'), the hot keys' high tables), then the walk fd_dsmh_kernel with the head of the
    slow list in its first blocks, and fd_dsm_slow_kernel for the rest.  With fixed-base keys (kf) also
-   fd_keyclass_kernel ahead of the split, fd_ftab_kernel ahead of the walk and the R-check chain behind it. */
+   fd_keyclass_kernel and fd_keyclaim_kernel ahead of the split, fd_ftab_kernel ahead of the walk and the R-check
+   chain behind it; the tables stay in the context's key cache, so a batch builds only the keys it
+   did not find there. */
 static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   u32 nsig = b.nsig; unsigned sg = b.sg; i8 * code = b.code; hipStream_t st = b.st;
   int kd = ctx->key_dedup, ks = ctx->key_split, kf = ctx->key_fixed;   /* (ks needs kd, kf needs ks) */
@@ -3258,22 +3405,45 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
      cold blocks (at most sg + 1 of them) */
   u32 const * arep = kd ? ctx->d_arep : NULL, * order = ks ? ctx->d_order : NULL, * hidx = ks ? ctx->d_hidx : NULL;
   u32 const * kscnt = ks ? slow_word( ctx, FD_SW_HOT ) : NULL;
+  /* kf: the worst case of keys that can be fixed-base in this batch, min( nsig / fb_min, fb_cap ): it sizes the grids
+     of fd_keyclaim_kernel, of fbase_build's blocks and of fd_ftab_kernel */
+  unsigned long fkeys = kf ? nsig / ctx->fb_min : 0UL; if( fkeys > ctx->fb_cap ) fkeys = ctx->fb_cap;
+  fd_kcache kc = {}; unsigned iblk = 0u;
   if( kd ) {
     /* the table cleared for this batch -- the smallest power of two of slots that is twice its signatures, so a
        small batch on a large context clears little -- then (ks) the signatures per key counted and the batch
        partitioned into hot and cold */
     u32 slots = 64u;
     if( !ctx->kd_tiny ) while( slots < ctx->kd_slots && slots < 2u*nsig ) slots <<= 1;
-    HIPCHK( hipMemsetAsync( ctx->d_ktab, 0, (size_t)slots * sizeof(u32), st ), -3 );
+    /* kf: the key cache's index of this batch in front of the table, cleared with it.  With the cache off, or after a
+       launch that failed (a slot claimed but never built), every slot is emptied first: every key then misses and
+       builds, with the same kernels and launches */
+    if( kf ) {
+      kc.key = ctx->d_skey; kc.state = ctx->d_sstate; kc.birth = ctx->d_sbirth; kc.stat = ctx->d_sstat; kc.idx = ctx->d_kidx;
+      kc.imask = ctx->kc_iwords - 1u; kc.iprobes = ctx->kc_iprobes; kc.fcap = ctx->fb_cap;
+      if( !++ctx->kc_batch ) { ctx->kc_batch = 1u; ctx->kc_dirty = 1; }        /* (the number wrapped: old stamps mean nothing) */
+      kc.batch = ctx->kc_batch;
+      int clear = ctx->kc_mode == 1 || ctx->kc_dirty;
+      ctx->kc_dirty = 2;                                   /* (until launch_batch has launched all of this batch) */
+      if( clear ) HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, ( ctx->fb_cap ? ctx->fb_cap : 1UL ) * 2 * sizeof(u32), st ), -3 );
+      iblk = ( ctx->fb_cap + FD_WG - 1u ) / FD_WG;
+    }
+    HIPCHK( hipMemsetAsync( kf ? ctx->d_kidx : ctx->d_ktab, 0, ( (size_t)slots + ( kf ? ctx->kc_iwords : 0u ) ) * sizeof(u32), st ), -3 );
     if( ks ) HIPCHK( hipMemsetAsync( ctx->d_kcnt, 0, (size_t)nsig * sizeof(u32), st ), -3 );
-    hipLaunchKernelGGL( ( ks ? fd_keydedup_kernel<1> : fd_keydedup_kernel<0> ), dim3(sg), dim3(FD_WG), 0, st, b.d_payload,
-                        b.d_desc, ctx->d_map, nsig, ctx->d_ktab, slots - 1u, ++ctx->kd_seed, ctx->kd_probes, ctx->d_arep,
+    u32 seed = ++ctx->kd_seed;
+    hipLaunchKernelGGL( ( ks ? fd_keydedup_kernel<1> : fd_keydedup_kernel<0> ), dim3(iblk + sg), dim3(FD_WG), 0, st, b.d_payload,
+                        b.d_desc, ctx->d_map, nsig, ctx->d_ktab, slots - 1u, seed, ctx->kd_probes, ctx->d_arep,
                         ctx->d_ulist, ucnt, ctx->d_pstat, FD_KD_SBLK( sg ), ks ? ctx->d_kcnt : (u32 *)NULL,
-                        kf && ctx->fb_min > ctx->hot_min ? ctx->fb_min : ks ? ctx->hot_min : 0u );
-    if( kf )
+                        kf && ctx->fb_min > ctx->hot_min ? ctx->fb_min : ks ? ctx->hot_min : 0u, (u32)iblk, kc );
+    if( kf ) {
       hipLaunchKernelGGL( fd_keyclass_kernel, dim3(sg), dim3(FD_WG), 0, st, (u32 const *)ctx->d_ulist, (u32 const *)ucnt,
-                          (u32 const *)ctx->d_kcnt, ctx->fb_min, ctx->d_fidx, ctx->d_flist, slow_word( ctx, FD_SW_HOT ),
-                          ctx->fb_cap );
+                          (u32 const *)ctx->d_kcnt, ctx->fb_min, ctx->d_fidx, ctx->d_mlist, slow_word( ctx, FD_SW_HOT ),
+                          b.d_payload, b.d_desc, (u32 const *)ctx->d_map, seed, ctx->d_astat, kc );
+      if( fkeys )
+        hipLaunchKernelGGL( fd_keyclaim_kernel, dim3( (unsigned)( ( fkeys + FD_WG - 1UL ) / FD_WG ) ), dim3(FD_WG), 0, st,
+                            (u32 const *)ctx->d_mlist, slow_word( ctx, FD_SW_HOT ), ctx->d_fidx, ctx->d_flist, b.d_payload,
+                            b.d_desc, (u32 const *)ctx->d_map, kc );
+    }
     if( ks )
       hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
                           (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
@@ -3287,14 +3457,16 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       b.d_payload, b.d_desc, ctx->d_map, nsig, 1, ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, ctx->d_tab, ctx->d_tabR,
                       kd ? (u32 const *)ctx->d_ulist : NULL, kd ? ucnt : (u32 *)NULL,
                       kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u, kf ? order : (u32 const *)NULL,
-                      (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL );
+                      (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL,
+                      (u32 const *)( kf ? ctx->d_kcnt : NULL ), kf ? ctx->fb_min : 0u, (u32 const *)( kf ? ctx->d_fidx : NULL ),
+                      (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch );
   if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
   /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
      keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
   unsigned hb = ks ? (unsigned)( ( 2UL * ( nsig / ctx->hot_min ) + FD_WG - 1 ) / FD_WG ) : 0u;
   /* kf: likewise the fixed-base keys' [2^(32t)](-A) in the next fbk blocks (eight lanes per key, the worst case of
-     min( nsig / fb_min, fb_cap ) keys); their entries after the hash (fd_ftab_kernel: two keys per block) */
-  unsigned long fkeys = kf ? nsig / ctx->fb_min : 0UL; if( fkeys > ctx->fb_cap ) fkeys = ctx->fb_cap;
+     min( nsig / fb_min, fb_cap ) keys); their entries after the hash (fd_ftab_kernel: two keys per block).  Both run
+     over the keys that claimed a slot in this batch: none, when every key was resident */
   unsigned fbk = (unsigned)( ( 8UL * fkeys + FD_WG - 1 ) / FD_WG );
   hipLaunchKernelGGL( ( ks ? fd_hashh_kernel<1> : fd_hashh_kernel<0> ), dim3( ks ? hb + fbk + sg + ( kf ? 2 : 1 ) : sg ),
                       dim3(FD_WG), 0, st,
@@ -3304,9 +3476,9 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       (u32 const *)( ks ? ctx->d_hlist : NULL ), (uint4 const *)( ks ? ctx->d_Axy : NULL ),
                       ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb, (u32 const *)( kf ? ctx->d_orderh : NULL ),
                       (u32 const *)( kf ? ctx->d_flist : NULL ), kf ? ctx->d_fbase : (uint4 *)NULL, (u32)fbk,
-                      kf ? ctx->fb_cap : 0u, kf ? ctx->d_Rxy : (uint4 *)NULL );
+                      kf ? ctx->d_sstat : (unsigned char *)NULL, kf ? ctx->d_Rxy : (uint4 *)NULL );
   if( fkeys )
-    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( fkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt, ctx->fb_cap,
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( fkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt,
                         (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_astat, (uint4 const *)ctx->d_fbase,
                         ctx->d_ftab );
   if( ctx->timing ) hipEventRecord( b.ev[1], st );
@@ -3350,7 +3522,8 @@ static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   u32 * slow_cnt = slow_word( ctx, FD_SW_SLOW );
   hipLaunchKernelGGL( fd_decode_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig, 0,
                       ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
-                      (u32 *)NULL, (unsigned char *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL );
+                      (u32 *)NULL, (unsigned char *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL,
+                      (u32 const *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, 0u );
   hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig,
                       ctx->semantics, 1, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
                       (uint4 const *)ctx->d_khash );
@@ -3394,20 +3567,21 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
     hipLaunchKernelGGL( fd_reduce_kernel, dim3(tg), dim3(FD_WG), 0, st, d_desc, (u32)txn_cnt, b.nsig, b.code, d_pflag, d_txn_out );
   if( ctx->timing ) hipEventRecord( b.ev[3], st );
   HIPCHK( hipGetLastError(), -3 );
+  if( ctx->kc_dirty == 2 ) ctx->kc_dirty = 0;           /* (launch_half: every launch of the batch was taken) */
   return 0;
 }
 
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
 fdgpu_debug_set_opts( fdgpu_debug_opts_t const * opts ) {
   std::lock_guard<std::mutex> lk( g_dbg_mu );
   if( opts ) g_dbg = *opts;
-  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 }
 
 /* staging + device buffers of async slot i (once) */
@@ -3489,7 +3663,21 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
       if( dbg.key_dedup != 2 ) while( slots < 2UL*ns && slots < ( 1UL << 31 ) ) slots <<= 1;
       ctx->kd_slots = (u32)slots; ctx->kd_tiny = dbg.key_dedup == 2; ctx->kd_probes = ctx->kd_tiny ? 2u : FD_KD_PROBES;
       ctx->kd_seed = 0u;
-      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ktab, slots * sizeof(u32) ), -1 );           /* (cleared per batch, launch_batch) */
+      /* the fixed-base keys' choices (below), ahead of the table: the key cache's per-batch index lies in front of it,
+         so that one memset clears both.  fdgpu_debug_opts_t.key_cache = 2 (tests): 8 slots, 8 words, 2 probes */
+      ctx->key_fixed = dbg.key_split != 1 && dbg.key_fixed != 1 && !ctx->half_force_slow;
+      if( ctx->key_fixed ) {
+        ctx->fb_min = dbg.key_fixed == 2 ? 4u : FD_FB_MIN;
+        unsigned long fc = ns / ctx->fb_min;
+        ctx->fb_cap = (u32)( fc < FD_FB_CAP ? fc : FD_FB_CAP );
+        ctx->kc_mode = dbg.key_cache; ctx->kc_dirty = 0; ctx->kc_batch = 0u;
+        if( ctx->kc_mode == 2 && ctx->fb_cap > 8u ) ctx->fb_cap = 8u;
+        u32 iw = 8u;
+        if( ctx->kc_mode != 2 ) while( iw < 4u * ctx->fb_cap ) iw <<= 1;
+        ctx->kc_iwords = iw; ctx->kc_iprobes = ctx->kc_mode == 2 ? 2u : FD_KD_PROBES;
+      }
+      HIPCHK( ctx_dev_alloc( ctx, &ctx->d_kidx, ( (size_t)ctx->kc_iwords + slots ) * sizeof(u32) ), -1 );   /* (cleared per batch, */
+      ctx->d_ktab = ctx->d_kidx + ctx->kc_iwords;                                                        /*  launch_half) */
       HIPCHK( ctx_dev_alloc( ctx, &ctx->d_arep, ns * sizeof(u32) ), -1 );
       HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ulist, ns * sizeof(u32) ), -1 );
       HIPCHK( ctx_dev_alloc( ctx, &ctx->d_astat, ns ), -1 );
@@ -3508,14 +3696,16 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
         /* the keys with many signatures get fixed-base tables (fd_keyclass_kernel) */
         /* (not under half_force_slow: that hook sends signatures down the half-size slow list, which a fixed-base
            signature never sees) */
-        ctx->key_fixed = dbg.key_fixed != 1 && !ctx->half_force_slow;
-        if( ctx->key_fixed ) {
-          ctx->fb_min = dbg.key_fixed == 2 ? 4u : FD_FB_MIN;
-          unsigned long fc = ns / ctx->fb_min;
-          ctx->fb_cap = (u32)( fc < FD_FB_CAP ? fc : FD_FB_CAP );
+        if( ctx->key_fixed ) {                          /* (fb_min, fb_cap and the key cache's choices: set above) */
           size_t fcn = ctx->fb_cap ? ctx->fb_cap : 1UL;
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fidx, ns * sizeof(u32) ), -1 );
-          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_flist, fcn * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_flist, fcn * 2 * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_skey, fcn * 8 * sizeof(u32) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sstate, fcn * 2 * sizeof(u32) ), -1 );
+          ctx->d_sbirth = ctx->d_sstate + fcn;
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sstat, fcn ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_mlist, ( ns / ctx->fb_min + 1UL ) * sizeof(u32) ), -1 );
+          HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, fcn * 2 * sizeof(u32), ctx->stream ), -1 );   /* every slot empty */
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_orderh, ns * sizeof(u32) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fbase, fcn * FD_FB_T * 8 * sizeof(uint4) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ftab, fcn * FD_FB_T * FD_FB_E * 6 * sizeof(uint4) ), -1 );
@@ -5048,6 +5238,19 @@ fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys
   if( cnt[0] > ctx->fb_cap ) cnt[0] = ctx->fb_cap;     /* (keys that claimed an index beyond the cap stayed hot) */
   if( fixed_keys ) *fixed_keys = (unsigned long)cnt[0];
   if( fixed_sigs ) *fixed_sigs = (unsigned long)cnt[1];
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, unsigned long * builds ) {
+  if( hits ) *hits = 0UL;
+  if( builds ) *builds = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_fixed || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 3 ] = { 0u, 0u, 0u };                         /* (hits, misses, builds) */
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_HIT, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( hits ) *hits = (unsigned long)cnt[0];
+  if( builds ) *builds = (unsigned long)cnt[2];
   return 0;
 }
 

@@ -413,6 +413,22 @@ fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, un
 int
 fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys, unsigned long * fixed_sigs );
 
+/* The key cache's part in the last batch launched on ctx.  A context keeps
+   the tables of its fixed-base keys from batch to batch, in as many slots
+   as a batch can have such keys: *hits = the batch's fixed-base keys whose
+   tables were found resident (nothing decoded, nothing built for them),
+   *builds = those that claimed a slot and built their tables in this
+   batch; together they are fixed_keys above.  Whether a key is fixed-base
+   in a batch is decided by that batch alone, as before.  A claim takes the
+   next slot, round a hand, that this batch has not used; nothing is read
+   back and nothing waits.  The cache is the context's: a context's batches
+   must be submitted on one stream at a time (they already share its work
+   buffers), and a closed context's keys are gone.  Both 0 when
+   fixed_count's are, and hits 0 with fdgpu_debug_opts_t.key_cache = 1.
+   Waits for the batch; 0 on success. */
+int
+fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, unsigned long * builds );
+
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
                     unsigned long *       out_tags,
@@ -768,6 +784,11 @@ typedef struct fdgpu_debug_opts {
                                         (A/B: exactly the kernels and launches without it); 2 = TESTS, fixed-base from
                                         4 signatures on.  Off whenever half_force_slow is set: a fixed-base signature
                                         has no half-size scalars and so never reaches that list */
+  int           key_cache;           /* half-size throughput path with key_fixed on: 0 = default, a context keeps its
+                                        fixed-base keys' tables from batch to batch (fdgpu_ed25519_fcache_count); 1 = off,
+                                        every slot is emptied ahead of each batch, so every key builds its tables (A/B:
+                                        the same kernels and launches); 2 = TESTS, 8 slots and an 8-word index with two
+                                        probes, so a few keys evict each other and some residents cannot be found */
 } fdgpu_debug_opts_t;
 
 void

@@ -2,7 +2,9 @@
 """Key mixes for the fixed-base keys: what per-key tables gain or cost on batches other than the
 benchmark's.  Times fdgpu_ed25519_verify_txns_device on HBM-resident batches of single-signature 1232-byte
 transactions with fdgpu_debug_opts_t.key_fixed on (0) and off (1), two contexts of one build interleaved
-(on off off on ...), tools/keysplit_mix.py's way and with its batches:
+(on off off on ...), tools/keysplit_mix.py's way and with its batches.  Each row repeats one batch, so from its
+second step on the on context finds every table in its key cache: the on column is a warm cache's
+time; tools/keycache_mix.py has the cold one (key_cache off) and the batches that evict:
 
   exactK     every key at exactly K signatures (exact128: FD_FB_MIN, the row that confirms or moves the bound;
              more keys than FD_FB_CAP = 4,096 ask for tables then, and the surplus stays hot);
