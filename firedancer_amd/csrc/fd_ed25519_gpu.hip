@@ -129,7 +129,7 @@
 #define FD_KS_NW   FD_LAT_SKEW_NW    /* windows stored for it: digA rows [0, 2 W + NW), digR rows [0, NW) */
 
 /* Fixed-base keys: a key with at least this many signatures in a batch gets comb tables of its own,
-   FD_FB_T tables of [1..FD_FB_E]( [2^(32 t)](-A) ) in affine precomputed form (96 B an entry, 96 KB a key), and its
+   FD_FB_T tables of [1..FD_FB_E]( [2^(32 t)](-A) ) in affine precomputed form (96 B an entry, 96 KB for the eight), and its
    signatures walk 24 doublings.  Reasoned, not measured: the tables cost about 1,100 field multiplies of wave
    time per key (the chain of up to 224 doublings shared by 8 keys of a wave, two waves of entries with an
    inversion each) and a signature saves about 880 / 64 of that, which puts the break-even near 80 signatures.
@@ -141,7 +141,11 @@
 #endif
 #define FD_FB_T    8
 #define FD_FB_E    128
-#define FD_FB_CAP  4096u              /* the most fixed-base keys of a batch (400 MB of tables); a key beyond stays hot */
+/* A slot of the key cache has room for FD_FB_NT = 32 tables (fd_gpu_lattice.h), one per byte of k: table j =
+   [1..128]( [2^(8j)](-A) ), 384 KB a slot.  A claim builds group 0, the FD_FB_T tables j = 0 (mod 4) above; a key found
+   resident in a later batch is promoted (fd_keyclass_kernel), groups 1..3 are built, and its signatures then walk
+   no doubling at all (dsmf_full). */
+#define FD_FB_CAP  4096u              /* the most fixed-base keys of a batch (1.5 GiB of slots); a key beyond stays hot */
 #define FD_FB_NONE 0xffffffffu        /* fidx[] of a representative whose key is not fixed-base */
 #define FD_PEND_FBREQ 5               /* per-signature code in flight: a fixed-base signature whose P's encoding != R's bytes */
 
@@ -250,6 +254,11 @@ FD_DEV u32 ks_sig( u32 const * __restrict__ order, u32 const * __restrict__ orde
 #define FD_KC_BUILD 8
 #define FD_KC_HAND0 9
 #define FD_KC_HAND  10
+/* ... and the full slots' (DESIGN 18): the promotion tickets drawn (those below pmax list their slot in plist[]), the
+   fixed-base keys whose slot is full, the signatures that walked without doublings */
+#define FD_KC_PTIX  11
+#define FD_KC_FFK   12
+#define FD_KC_FFS   13
 
 /* ------------------------------------------------------------------ */
 
@@ -360,7 +369,10 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
                   u32                                   fb_min,
                   u32 const *              __restrict__ fidx,
                   u32 const *              __restrict__ birth,
-                  u32                                   batch ) {
+                  u32                                   batch,
+                  /* ... and counts the fixed-base keys whose slot is full (ucnt + 3 are the FD_KC_* words):
+                     the classification and the claims are over, so full[] no longer changes in this batch */
+                  u32 const *              __restrict__ full ) {
   u32 s, is_r;
   unsigned char * st;
   if( ulist ) {
@@ -382,6 +394,7 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
       s = ulist[i]; is_r = 0u; st = astat + s;
       if( fidx && kcnt[s] >= fb_min ) {
         u32 slot = fidx[s];
+        if( slot != FD_FB_NONE && full[slot] ) atomicAdd( ucnt + 3 + FD_KC_FFK, 1u );
         if( slot != FD_FB_NONE && birth[slot] != batch ) return;
       }
     } else if( order ) {
@@ -871,11 +884,23 @@ FD_DEV void hashf_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
   (void)store_digits_B( Sw, col, n, digB, 0, []( int ) { return 0; } );
 }
 
-/* P_t = [2^(32t)](-A) of fixed-base key fi in the -A table's entry format at fbase[8 fi + t], from the
-   representative's canonical affine A: one lane per (key, t), so the chain of up to 224 doublings is paid by 8
-   lanes of a key and not by the 1,024 that build its entries */
+/* P_j = [2^(8j)](-A) of the key in slot fi in the -A table's entry format at fbase[32 fi + j]: A doubled nd times.  A
+   claim runs one lane per (key, t) with j = 4t from the representative's canonical affine A (fbase_build), so the
+   chain of up to 224 doublings is paid by 8 lanes of a key and not by the 1,024 that build its entries. */
 template<int FM = FD_CARRY_FOLD>
-FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 t, uint4 const * __restrict__ Axy, u32 rep ) {
+FD_DEV void fbase_chain( uint4 * __restrict__ fbase, u32 fi, u32 j, ge_p3 & A, int nd ) {
+#pragma unroll 1
+  for( int i=0; i<nd; i++ ) ge_p3_dbl<FM>( A, A );
+  ge_cached c;
+  ge_p3_to_cached<FM>( c, A );
+  uint4 * b = fbase + ( (size_t)fi * FD_FB_NT + j ) * 8;
+  fe_store_packed( b + 0, c.YpX );
+  fe_store_packed( b + 2, c.YmX );
+  fe_store_packed( b + 4, c.Z   );
+  fe_store_packed( b + 6, c.T2d );
+}
+template<int FM = FD_CARRY_FOLD>
+FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 j, uint4 const * __restrict__ Axy, u32 rep ) {
   uint4 const * ap = Axy + (size_t)rep*4;
   ge_p3 A;
   fe_from_quads( A.X, ap[0], ap[1] );
@@ -883,25 +908,16 @@ FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 t, uint4 const 
   A.Z = fe_one();
   fe_neg( A.X, A.X ); fe_wcarry( A.X, A.X );              /* -A */
   fe_mul<FM>( A.T, A.X, A.Y );
-  int nd = 32*(int)t;
-#pragma unroll 1
-  for( int i=0; i<nd; i++ ) ge_p3_dbl<FM>( A, A );
-  ge_cached c;
-  ge_p3_to_cached<FM>( c, A );
-  uint4 * b = fbase + ( (size_t)fi * FD_FB_T + t ) * 8;
-  fe_store_packed( b + 0, c.YpX );
-  fe_store_packed( b + 2, c.YmX );
-  fe_store_packed( b + 4, c.Z   );
-  fe_store_packed( b + 6, c.T2d );
+  fbase_chain<FM>( fbase, fi, j, A, 8*(int)j );
 }
 
 /* the identity in affine precomputed form (y+x = y-x = 1, 2dxy = 0), packed like a table entry: digit 0 */
 __device__ __attribute__(( aligned( 16 ) )) unsigned const fd_ptab_ident_w[ 24 ] = {
   1u,0u,0u,0u, 0u,0u,0u,0u,  1u,0u,0u,0u, 0u,0u,0u,0u,  0u,0u,0u,0u, 0u,0u,0u,0u };
 
-/* entry e >= 1 of table t of fixed-base key fi: 6 uint4 (ypx, ymx, xy2d, canonical, packed 8x32) */
-FD_DEV size_t ftab_at( u32 fi, u32 t, u32 e ) {
-  return ( ( (size_t)fi * FD_FB_T + t ) * FD_FB_E + ( e - 1u ) ) * 6;
+/* entry e >= 1 of table j (of FD_FB_NT) of the key in slot fi: 6 uint4 (ypx, ymx, xy2d, canonical, packed 8x32) */
+FD_DEV size_t ftab_at( u32 fi, u32 j, u32 e ) {
+  return ( ( (size_t)fi * FD_FB_NT + j ) * FD_FB_E + ( e - 1u ) ) * 6;
 }
 
 /* fd_ftab_kernel's two passes over a lane's eight points, written as recursions over the point's number so
@@ -936,9 +952,10 @@ FD_DEV void ftab_pass2( fe & inv, uint4 * __restrict__ ent, fe const (&pf)[ 8 ] 
   if constexpr( I > 0 ) ftab_pass2<I-1>( inv, ent, pf );
 }
 
-/* The entries of the fixed-base keys' tables: 128 lanes per key (a workgroup holds two keys), lane (t, g) with
-   g = 0..15 builds entries 8g + 1 .. 8g + 8 of table t.  It starts at [8g]P_t by double-and-add over g's 4 bits
-   and three doublings, adds P_t eight times, and normalises its eight points with Montgomery's trick: the
+/* The entries of the fixed-base keys' tables: 128 lanes per work item (slot, group r) -- a workgroup holds two
+   items -- lane (t, g) with g = 0..15 builds entries 8g + 1 .. 8g + 8 of the slot's table j = 4t + r (a claim lists
+   group 0, a promotion groups 1..3: DESIGN 18).  It starts at [8g]P_j by double-and-add over g's 4 bits
+   and three doublings, adds P_j eight times, and normalises its eight points with Montgomery's trick: the
    product of its own eight Z, the products of the other lanes' through lane-shuffle prefix and suffix products
    as in fd_rprod_kernel, one inversion per wave (every lane computes it: no lane of the wave has anything else
    to do), then 1/Z_i = (prefix of the lane's Z below i) x (running inverse).  Blocks beyond the device-side count
@@ -946,18 +963,28 @@ FD_DEV void ftab_pass2( fe & inv, uint4 * __restrict__ ent, fe const (&pf)[ 8 ] 
    signatures' codes are final or parked before any walk). */
 __global__ void __launch_bounds__( FD_WG, 2 )          /* (two waves per SIMD asked for: the eight prefix products are 80 VGPRs) */
 fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 const * __restrict__ flist,
-                unsigned char const * __restrict__ astat, uint4 const * __restrict__ fbase, uint4 * __restrict__ ftab ) {
-  u32 nk = kscnt[FD_KC_BUILD];                            /* the keys that claimed a slot in this batch */
+                unsigned char const * __restrict__ astat, uint4 const * __restrict__ fbase, uint4 * __restrict__ ftab,
+                /* a work item is (slot, group r), the 8 tables j = 4t + r of the slot.  Items [0, cg nk)
+                   are the claims' groups 0..cg-1 (cg = 1; 4 with fdgpu_debug_opts_t.key_full = 2); the items after
+                   them are groups 1..3 of the slots promoted in this batch (plist[], at most pmax) */
+                u32 cg, u32 const * __restrict__ plist, u32 pmax ) {
+  u32 nk = kscnt[FD_KC_BUILD] * cg;                       /* the keys that claimed a slot in this batch */
+  u32 np = kscnt[FD_KC_PTIX]; np = np < pmax ? np : pmax;
   u32 bi = blockIdx.x * 2u + ( threadIdx.x >> 7 );
-  if( blockIdx.x * 2u >= nk ) return;                     /* (block-uniform) */
-  /* a wave is of one key: lanes of a key that is beyond the count, or has no table, skip the work together */
-  if( bi >= nk || ( astat[ flist[2u*bi+1u] ] & 7u ) ) return;
-  u32 fi = flist[2u*bi];                                  /* its slot */
-  u32 t = ( threadIdx.x >> 4 ) & 7u, g = threadIdx.x & 15u;
+  if( blockIdx.x * 2u >= nk + 3u*np ) return;             /* (block-uniform) */
+  /* a wave is of one item: lanes of an item that is beyond the count, or of a key without tables, skip the work
+     together */
+  if( bi >= nk + 3u*np ) return;
+  u32 fi, grp;
+  if( bi < nk ) {
+    if( astat[ flist[ 2u*( bi / cg ) + 1u ] ] & 7u ) return;
+    fi = flist[ 2u*( bi / cg ) ]; grp = bi % cg;          /* its slot */
+  } else { fi = plist[ ( bi - nk ) / 3u ]; grp = ( bi - nk ) % 3u + 1u; }   /* (promoted: the slot has tables) */
+  u32 t = 4u*( ( threadIdx.x >> 4 ) & 7u ) + grp, g = threadIdx.x & 15u;
   int lane = (int)( threadIdx.x & 63u );
   ge_cached pc;
   {
-    atab_raw r; uint4 const * b = fbase + ( (size_t)fi * FD_FB_T + t ) * 8;
+    atab_raw r; uint4 const * b = fbase + ( (size_t)fi * FD_FB_NT + t ) * 8;
 #pragma unroll
     for( int i=0; i<8; i++ ) r.q[i] = b[i];
     atab_unpack( pc, r );
@@ -1029,10 +1056,11 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
                  /* fixed-base keys (orderh = NULL: none): */
                  u32 const *              __restrict__ orderh,   /* the hot signatures as the split listed them */
                  u32 const *              __restrict__ flist,    /* (slot, representative) of the keys claimed in this batch */
-                 uint4 *                  __restrict__ fbase,    /* [slot][8] [2^(32t)](-A) */
-                 u32                                   fblk,     /* blocks [hblk,hblk+fblk) build them: one lane per (key, t) */
+                 uint4 *                  __restrict__ fbase,    /* [slot][32] [2^(8j)](-A) */
+                 u32                                   fblk,     /* blocks [hblk,hblk+fblk) build them: lpk lanes per key */
                  unsigned char *          __restrict__ sstat,    /* [slot] the key's decode status */
-                 uint4 *                  __restrict__ Rraw ) {
+                 uint4 *                  __restrict__ Rraw,
+                 u32                                   lpk ) {   /* lanes per claimed key: 8 (j = 4t), or 32 (every j) */
   if( KS ) {
     if( blockIdx.x < hblk ) {
       /* dispatched first, so the chains of 68 and 136 doublings run beside the hash and not after it.  A key that
@@ -1049,11 +1077,14 @@ fd_hashh_kernel( unsigned char const *    __restrict__ payload,
       u32 i = ( blockIdx.x - hblk ) * FD_WG + threadIdx.x;
       /* (of the keys that claimed a slot in this batch, by slot; the slot records the key's status,
          whether or not it decodes, for the batches that find it resident) */
-      if( ( i >> 3 ) >= kscnt[FD_KC_BUILD] ) return;
-      u32 slot = flist[ 2u*( i >> 3 ) ], rep = flist[ 2u*( i >> 3 ) + 1u ];
-      if( !( i & 7u ) ) sstat[slot] = astat[rep];
+      /* (lpk lanes per key, 8 for the tables j = 4t of group 0; 32 for all of them when a claim fills its
+         slot at once, fdgpu_debug_opts_t.key_full = 2) */
+      u32 k = i / lpk, q = i % lpk;
+      if( k >= kscnt[FD_KC_BUILD] ) return;
+      u32 slot = flist[ 2u*k ], rep = flist[ 2u*k + 1u ];
+      if( !q ) sstat[slot] = astat[rep];
       if( astat[rep] & 7u ) return;
-      fbase_build( fbase, slot, i & 7u, Axy, rep );
+      fbase_build( fbase, slot, q * ( (u32)FD_FB_NT / lpk ), Axy, rep );
       return;
     }
     u32 col, j; int cls;
@@ -1377,21 +1408,20 @@ FD_DEV void dsmf_one( u32 col, size_t n, u32 fi, uint4 const * __restrict__ ftab
   uint4 ra[ 6 ], rb[ 6 ];
 #pragma unroll 1
   for( int r=3; r>=0; r-- ) {
-    int na = ( r & 1 ) ? FD_FB_T : 2*FD_FB_T;          /* adds of this step: 8 from the key's tables, then 8 from B's */
-    int d = dA[ (size_t)r*n ];
-    ptab_fetch( ra, d ? ftab + ftab_at( fi, 0u, (u32)( d < 0 ? -d : d ) ) : (uint4 const *)fd_ptab_ident_w );
+    int na = fd_fb_old_adds( r );                      /* adds of this step: 8 from the key's tables, then 8 from B's */
+    int d = dA[ (size_t)fd_fb_old_digit( r, 0 )*n ];
+    ptab_fetch( ra, d ? ftab + ftab_at( fi, (u32)fd_fb_old_table( 0 ), (u32)fd_fb_entry( d ) ) : (uint4 const *)fd_ptab_ident_w );
 #pragma unroll 1
     for( int i=0; i<na; i++ ) {
       int dn = 0;
       if( i + 1 < na ) {                               /* the next add's entry, in flight during this one */
         int i1 = i + 1;
-        if( i1 < FD_FB_T ) {
-          dn = dA[ (size_t)( 4*i1 + r )*n ];
-          ptab_fetch( rb, dn ? ftab + ftab_at( fi, (u32)i1, (u32)( dn < 0 ? -dn : dn ) ) : (uint4 const *)fd_ptab_ident_w );
+        if( !fd_fb_old_is_base( i1 ) ) {               /* (the slot's tables 4t and the base point's 2t: fd_gpu_lattice.h) */
+          dn = dA[ (size_t)fd_fb_old_digit( r, i1 )*n ];
+          ptab_fetch( rb, dn ? ftab + ftab_at( fi, (u32)fd_fb_old_table( i1 ), (u32)fd_fb_entry( dn ) ) : (uint4 const *)fd_ptab_ident_w );
         } else {
-          int tb = i1 - FD_FB_T;
-          dn = dB[ (size_t)( 2*tb + ( r >> 1 ) )*n ];
-          ptab_fetch( rb, btabf + ( (size_t)tb * FD_BTAB_ENTRIES + (size_t)( dn < 0 ? -dn : dn ) ) * 6 );
+          dn = dB[ (size_t)fd_fb_old_digit( r, i1 )*n ];
+          ptab_fetch( rb, btabf + ( (size_t)fd_fb_old_table( i1 ) * FD_BTAB_ENTRIES + (size_t)fd_fb_entry( dn ) ) * 6 );
         }
       }
       ge_precomp q;
@@ -1412,6 +1442,52 @@ FD_DEV void dsmf_one( u32 col, size_t n, u32 fi, uint4 const * __restrict__ ftab
       for( int b=0; b<7; b++ ) { ge_dbl<FM>( t, P2 ); ge_p1p1_to_p2<FM>( P2, t ); }
       ge_dbl<FM>( t, P2 ); ge_p1p1_to_p3<FM>( P, t );
     }
+  }
+  fe_store_planar( Pbuf + col, n, P.X );
+  fe_store_planar( Pbuf + 10*n + col, n, P.Y );
+  fe_store_planar( Pbuf + 20*n + col, n, P.Z );
+}
+
+/* The walk of a fixed-base signature whose key's slot is full: every byte of k has a table of its own
+   and every 16-bit digit of S one of the base point's, so P = [S]B + [k](-A) is the sum of 32 + 16 entries with no
+   doubling at all.  Addition i reads what fd_fb_full_digit / fd_fb_full_table say (two of the key's, then one of
+   the base point's).  Each 96-byte entry is gathered one addition ahead; the loop takes two additions a turn, so
+   the two raw entries never move.  (A third raw entry, gathered two ahead, costs the third wave: 120 B of
+   scratch.)  P is stored as dsmf_one stores it. */
+FD_DEV void full_fetch( uint4 r[ 6 ], int & d, int i, size_t n, u32 fi, uint4 const * __restrict__ ftab,
+                        uint4 const * __restrict__ btabf, i8 const * __restrict__ dA, short const * __restrict__ dB ) {
+  if( !fd_fb_full_is_base( i ) ) {
+    d = dA[ (size_t)fd_fb_full_digit( i )*n ];
+    ptab_fetch( r, d ? ftab + ftab_at( fi, (u32)fd_fb_full_table( i ), (u32)fd_fb_entry( d ) ) : (uint4 const *)fd_ptab_ident_w );
+  } else {
+    d = dB[ (size_t)fd_fb_full_digit( i )*n ];
+    ptab_fetch( r, btabf + ( (size_t)fd_fb_full_table( i ) * FD_BTAB_ENTRIES + (size_t)fd_fb_entry( d ) ) * 6 );
+  }
+}
+template<int FM>
+FD_DEV void full_add( ge_p3 & P, uint4 const r[ 6 ], int d ) {
+  ge_precomp q;
+  fe_from_quads( q.ypx,  r[0], r[1] );
+  fe_from_quads( q.ymx,  r[2], r[3] );
+  fe_from_quads( q.xy2d, r[4], r[5] );
+  ge_precomp_cneg( q, d < 0 );
+  ge_p1p1 t;
+  ge_add_precomp<FM>( t, P, q ); ge_p1p1_to_p3<FM>( P, t );
+}
+template<int FM>
+FD_DEV void dsmf_full( u32 col, size_t n, u32 fi, uint4 const * __restrict__ ftab, uint4 const * __restrict__ btabf,
+                       i8 const * __restrict__ digA, short const * __restrict__ digB, u32 * __restrict__ Pbuf ) {
+  ge_p3 P; ge_p3_identity( P );
+  i8 const * dA = digA + col; short const * dB = digB + col;
+  uint4 ra[ 6 ], rb[ 6 ];
+  int da, db;
+  full_fetch( ra, da, 0, n, fi, ftab, btabf, dA, dB );
+#pragma unroll 1
+  for( int i=0; i<FD_FB_FULL_ADDS; i+=2 ) {
+    full_fetch( rb, db, i + 1, n, fi, ftab, btabf, dA, dB );
+    full_add<FM>( P, ra, da );
+    if( i + 2 < FD_FB_FULL_ADDS ) full_fetch( ra, da, i + 2, n, fi, ftab, btabf, dA, dB );
+    full_add<FM>( P, rb, db );
   }
   fe_store_planar( Pbuf + col, n, P.X );
   fe_store_planar( Pbuf + 10*n + col, n, P.Y );
@@ -1447,8 +1523,10 @@ fd_dsmh_kernel( u32                      nsig,
                 /* fixed-base keys (fidx = NULL: none; the grid is then nslowblk + sg + 2 blocks): */
                 u32 const *   __restrict__ fidx,         /* a fixed-base representative's dense index */
                 uint4 const * __restrict__ ftab,         /* the keys' tables (fd_ftab_kernel) */
-                uint4 const * __restrict__ btabf,        /* [8][0..32768]([2^(32t)]B) */
-                u32 *         __restrict__ Pbuf ) {      /* P of a fixed-base signature, at its place */
+                uint4 const * __restrict__ btabf,        /* [16][0..32768]([2^(16u)]B) */
+                u32 *         __restrict__ Pbuf,         /* P of a fixed-base signature, at its place */
+                u32 const *   __restrict__ full,         /* [slot] 0: tables j = 0 (mod 4) only, else all 32 */
+                u32 *         __restrict__ ffcnt ) {     /* the signatures that walked without doublings (FD_KC_FFS) */
   size_t n = nsig;
   if( blockIdx.x < nslowblk ) {
     /* the first blocks take the head of the slow list (full 253-bit walk,
@@ -1468,8 +1546,19 @@ fd_dsmh_kernel( u32                      nsig,
     in = ks_pos( blockIdx.x - nslowblk, nsig, fidx ? kscnt[FD_KC_FB] : 0u, kscnt[FD_KC_HOT], col, j, cls );
     s = in ? order[col] : 0u;
     if( cls==2 ) {                                      /* (block-uniform) a fixed-base block: pending = SUCCESS so far */
-      if( in && code[s] == FD_ED25519_SUCCESS )
-        dsmf_one<FM>( col, n, fidx[ arep[s] ], ftab, btabf, (i8 const *)digA, digB, Pbuf );
+      /* before any lane leaves, the wave votes.  When every lane that walks has a full slot, the wave
+         walks without doublings; one lane that does not, and it walks as before, from the tables j = 0 (mod 4)
+         that every slot has.  The wave's count of such signatures: one no-return add by its first walking lane. */
+      int walk = in && code[s] == FD_ED25519_SUCCESS;
+      u32 fi = walk ? fidx[ arep[s] ] : 0u;
+      unsigned long long wm = __ballot( walk );
+      int allfull = __all( walk ? full[fi] != 0u : 1 );
+      if( !walk ) return;
+      if( allfull ) {
+        if( (int)( threadIdx.x & 63u ) == __ffsll( (long long)wm ) - 1 ) atomicAdd( ffcnt, (u32)__popcll( wm ) );
+        dsmf_full<FM>( col, n, fi, ftab, btabf, (i8 const *)digA, digB, Pbuf );
+      }
+      else dsmf_one<FM>( col, n, fi, ftab, btabf, (i8 const *)digA, digB, Pbuf );
       return;
     }
     hot = cls==1;
@@ -2497,6 +2586,11 @@ struct fd_kcache {
   u32             imask, iprobes;
   u32             fcap;      /* slots */
   u32             batch;     /* this batch's number, never 0 */
+  /* full slots */
+  u32 *           full;      /* [slot] 0 = the tables j = 0 (mod 4) only, else the batch that built the other 24 */
+  u32 *           plist;     /* [pmax] the slots promoted in this batch */
+  u32             pmax;      /* the most slots a batch promotes (0: none, fdgpu_debug_opts_t.key_full = 1) */
+  u32             fnow;      /* a claim builds all 32 tables at once (fdgpu_debug_opts_t.key_full = 2) */
 };
 
 template<int KS>
@@ -2544,7 +2638,8 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
   if( KS && !s ) {
     u32 * c = ucnt + 3;                                       /* (FD_KC_*: the three of the split, two of the fixed-base keys, */
     for( int k=0; k<5; k++ ) c[k] = 0u;                       /*  three of the key cache; the hand brought back below the slots */
-    for( int k=FD_KC_HIT; k<=FD_KC_BUILD; k++ ) c[k] = 0u;    /*  so that a batch's draws never wrap, and its start noted) */
+    for( int k=FD_KC_HIT; k<=FD_KC_BUILD; k++ ) c[k] = 0u;    /*  so that a batch's draws never wrap, and its start noted; */
+    for( int k=FD_KC_PTIX; k<=FD_KC_FFS; k++ ) c[k] = 0u;     /*  three of the full slots) */
     if( iblk ) { u32 h = c[FD_KC_HAND] % kc.fcap; c[FD_KC_HAND] = h; c[FD_KC_HAND0] = h; }
   }
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
@@ -2696,8 +2791,16 @@ fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucn
     if( diff ) continue;
     kc.state[slot] = kc.batch;
     fidx[s] = slot;
-    astat[s] = kc.stat[slot];
+    u32 stt = kc.stat[slot];
+    astat[s] = (unsigned char)stt;
     atomicAdd( cnt + FD_KC_FBK, 1u ); atomicAdd( cnt + FD_KC_HIT, 1u );
+    /* promotion: a hit is a key seen in an earlier batch.  A slot that has tables and is not full is
+       taken by one lane (the compare-and-swap: two representatives may share a key, and a slot is built once), which
+       draws a ticket; a ticket below pmax lists the slot, a later one gives the slot back for a following batch */
+    if( kc.pmax && !( stt & 7u ) && !kc.full[slot] && !atomicCAS( kc.full + slot, 0u, kc.batch ) ) {
+      u32 tk = atomicAdd( cnt + FD_KC_PTIX, 1u );
+      if( tk < kc.pmax ) kc.plist[tk] = slot; else kc.full[slot] = 0u;
+    }
     return;
   }
   fidx[s] = FD_FB_NONE;
@@ -2715,7 +2818,27 @@ fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucn
 __global__ void __launch_bounds__( FD_WG )
 fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 * __restrict__ fidx,
                     u32 * __restrict__ flist, unsigned char const * __restrict__ payload,
-                    fdgpu_txn_desc_t const * __restrict__ desc, u32 const * __restrict__ map, fd_kcache kc ) {
+                    fdgpu_txn_desc_t const * __restrict__ desc, u32 const * __restrict__ map, fd_kcache kc,
+                    u32 cblk, uint4 * __restrict__ fbase ) {
+  if( blockIdx.x >= cblk ) {
+    /* the blocks after the claims' (DESIGN 18): the promoted slots' P_j for j = 4t + r, r = 1..3, one lane per
+       (slot, j).  The key's A is not decoded in this batch, so the chain of 8r doublings starts from the slot's own
+       P_4t, which the batch that claimed the slot left in fbase[] in cached form: (Y+X, Y-X, Z) -> (2X : 2Y : 2Z);
+       a doubling reads no T.  plist[] and the ticket count are the launch before's (fd_keyclass_kernel). */
+    u32 i = ( blockIdx.x - cblk ) * FD_WG + threadIdx.x;
+    u32 np = cnt[FD_KC_PTIX]; np = np < kc.pmax ? np : kc.pmax;
+    u32 p = i / 24u, q = i % 24u;
+    if( p >= np ) return;
+    u32 slot = kc.plist[p], t = q / 3u, r = q % 3u + 1u;
+    uint4 const * e = fbase + ( (size_t)slot * FD_FB_NT + 4u*t ) * 8;
+    fe ypx, ymx; ge_p3 A;
+    fe_from_quads( ypx, e[0], e[1] ); fe_from_quads( ymx, e[2], e[3] ); fe_from_quads( A.Z, e[4], e[5] );
+    fe_sub( A.X, ypx, ymx ); fe_wcarry( A.X, A.X );
+    fe_add( A.Y, ypx, ymx ); fe_wcarry( A.Y, A.Y );
+    fe_add( A.Z, A.Z, A.Z ); fe_wcarry( A.Z, A.Z ); A.T = fe_zero();
+    fbase_chain( fbase, slot, 4u*t + r, A, 8*(int)r );
+    return;
+  }
   u32 i = blockIdx.x * FD_WG + threadIdx.x;
   if( i >= cnt[FD_KC_MISS] || i >= kc.fcap ) return;
   u32 s = mlist[i], hand0 = cnt[FD_KC_HAND0];
@@ -2731,6 +2854,7 @@ fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 
 #pragma unroll
     for( int k=0; k<8; k++ ) kc.key[ 8u*slot + k ] = w[k];
     kc.state[slot] = kc.batch; kc.birth[slot] = kc.batch;
+    kc.full[slot] = kc.fnow ? kc.batch : 0u;         /* (the tables j = 0 (mod 4) only, unless tests fill the slot) */
     fidx[s] = slot;
     u32 b = atomicAdd( cnt + FD_KC_BUILD, 1u );
     flist[2u*b] = slot; flist[2u*b+1u] = s;
@@ -3107,12 +3231,18 @@ struct fdgpu_ed25519_ctx {
   u32 *   d_sstate;              /*   [fb_cap] 0 = empty, else the batch that last used the slot; then [fb_cap] the batch that
                                       claimed it (d_sbirth) */
   u32 *   d_sbirth;
+  u32 *   d_sfull;               /*   ... then [fb_cap] 0 = the slot has its tables j = 0 (mod 4) only, else the batch that built the
+                                      other 24 */
+  int     kfull_mode;            /*   fdgpu_debug_opts_t.key_full: 0 on, 1 off (no slot is ever promoted), 2 tests (a claim fills
+                                      its slot at once) */
+  u32     pmax;                  /*   max( 1, fb_cap / 4 ): the most slots one batch promotes; 0 with key_full off */
+  u32 *   d_plist;               /*   [pmax] the slots promoted in this batch */
   unsigned char * d_sstat;       /*   [fb_cap] the key's decode status */
   u32 *   d_mlist;               /*   [max_sig / fb_min + 1] the representatives of this batch's misses */
   u32 *   d_orderh;              /*   [max_sig] the hot signatures as the split lists them (ks_sig) */
-  uint4 * d_fbase;               /*   [fb_cap][8][8] [2^(32t)](-A), cached form */
-  uint4 * d_ftab;                /*   [fb_cap][8][128][6] the keys' tables, 96 KB per key */
-  uint4 * d_btabf;               /*   [8][FD_BTAB_ENTRIES][6] [0..32768]([2^(32t)]B) */
+  uint4 * d_fbase;               /*   [fb_cap][32][8] [2^(8j)](-A), cached form */
+  uint4 * d_ftab;                /*   [fb_cap][32][128][6] the keys' tables, 384 KB per slot: 1.5 GiB at FD_FB_CAP */
+  uint4 * d_btabf;               /*   [16][FD_BTAB_ENTRIES][6] [0..32768]([2^(16u)]B), 50 MB */
   u32 *   d_fslow;               /*   [max_sig] the fixed-base places whose R needs its decode (fd_rslow_kernel) */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
@@ -3328,7 +3458,7 @@ enum {
   FD_SW_FBSLOW   = 9,   /* the count of the fixed-base R check's list (d_fslow) */
   FD_SW_KCACHE   = 10,  /* the key cache's hits, misses and builds, the hand's start and the hand (FD_KC_HIT.., counted from
                            FD_SW_HOT); the hand alone outlives a batch */
-  FD_SW_CNT      = 16 };
+  FD_SW_CNT      = 20 };                /* (... and the full slots' tickets, keys and signatures, DESIGN 18: FD_KC_PTIX..) */
 static u32 * slow_word( fdgpu_ed25519_ctx_t const * ctx, int w ) { return ctx->d_slow + ctx->max_sig + w; }
 
 /* What every kernel launch of one batch shares */
@@ -3379,7 +3509,8 @@ static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int la
                         ctx->d_digR, ctx->d_digB, ctx->d_btab, ctx->d_btab2, code, ctx->d_Rxy, ctx->d_slow, slow_cnt, 0u,
                         ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL, (u32 const *)NULL,
                         (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL,
-                        (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL, (u32 *)NULL );
+                        (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL, (u32 *)NULL, (u32 const *)NULL,
+                        (u32 *)NULL );
   else                                         /* one lane, full length (no carry fold up to nofold_max) */
     hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
                         nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 0 );
@@ -3423,9 +3554,10 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
       kc.imask = ctx->kc_iwords - 1u; kc.iprobes = ctx->kc_iprobes; kc.fcap = ctx->fb_cap;
       if( !++ctx->kc_batch ) { ctx->kc_batch = 1u; ctx->kc_dirty = 1; }        /* (the number wrapped: old stamps mean nothing) */
       kc.batch = ctx->kc_batch;
+      kc.full = ctx->d_sfull; kc.plist = ctx->d_plist; kc.pmax = ctx->pmax; kc.fnow = ctx->kfull_mode == 2;
       int clear = ctx->kc_mode == 1 || ctx->kc_dirty;
       ctx->kc_dirty = 2;                                   /* (until launch_batch has launched all of this batch) */
-      if( clear ) HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, ( ctx->fb_cap ? ctx->fb_cap : 1UL ) * 2 * sizeof(u32), st ), -3 );
+      if( clear ) HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, ( ctx->fb_cap ? ctx->fb_cap : 1UL ) * 3 * sizeof(u32), st ), -3 );   /* (state, birth, full) */
       iblk = ( ctx->fb_cap + FD_WG - 1u ) / FD_WG;
     }
     HIPCHK( hipMemsetAsync( kf ? ctx->d_kidx : ctx->d_ktab, 0, ( (size_t)slots + ( kf ? ctx->kc_iwords : 0u ) ) * sizeof(u32), st ), -3 );
@@ -3439,10 +3571,14 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
       hipLaunchKernelGGL( fd_keyclass_kernel, dim3(sg), dim3(FD_WG), 0, st, (u32 const *)ctx->d_ulist, (u32 const *)ucnt,
                           (u32 const *)ctx->d_kcnt, ctx->fb_min, ctx->d_fidx, ctx->d_mlist, slow_word( ctx, FD_SW_HOT ),
                           b.d_payload, b.d_desc, (u32 const *)ctx->d_map, seed, ctx->d_astat, kc );
-      if( fkeys )
-        hipLaunchKernelGGL( fd_keyclaim_kernel, dim3( (unsigned)( ( fkeys + FD_WG - 1UL ) / FD_WG ) ), dim3(FD_WG), 0, st,
+      if( fkeys ) {
+        /* (... and, in the blocks after, the P_j of the slots fd_keyclass_kernel promoted: 24 lanes a slot, the
+           worst case of pmax slots, blocks beyond the device-side count return at once) */
+        unsigned cblk = (unsigned)( ( fkeys + FD_WG - 1UL ) / FD_WG ), pbk = (unsigned)( ( 24UL * ctx->pmax + FD_WG - 1 ) / FD_WG );
+        hipLaunchKernelGGL( fd_keyclaim_kernel, dim3( cblk + pbk ), dim3(FD_WG), 0, st,
                             (u32 const *)ctx->d_mlist, slow_word( ctx, FD_SW_HOT ), ctx->d_fidx, ctx->d_flist, b.d_payload,
-                            b.d_desc, (u32 const *)ctx->d_map, kc );
+                            b.d_desc, (u32 const *)ctx->d_map, kc, (u32)cblk, ctx->d_fbase );
+      }
     }
     if( ks )
       hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
@@ -3459,15 +3595,19 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u, kf ? order : (u32 const *)NULL,
                       (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL,
                       (u32 const *)( kf ? ctx->d_kcnt : NULL ), kf ? ctx->fb_min : 0u, (u32 const *)( kf ? ctx->d_fidx : NULL ),
-                      (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch );
+                      (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch, (u32 const *)( kf ? ctx->d_sfull : NULL ) );
   if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
   /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
      keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
   unsigned hb = ks ? (unsigned)( ( 2UL * ( nsig / ctx->hot_min ) + FD_WG - 1 ) / FD_WG ) : 0u;
-  /* kf: likewise the fixed-base keys' [2^(32t)](-A) in the next fbk blocks (eight lanes per key, the worst case of
+  /* kf: likewise the fixed-base keys' [2^(32t)](-A) in the next fbk blocks (lpk = eight lanes per key, the worst case of
      min( nsig / fb_min, fb_cap ) keys); their entries after the hash (fd_ftab_kernel: two keys per block).  Both run
      over the keys that claimed a slot in this batch: none, when every key was resident */
-  unsigned fbk = (unsigned)( ( 8UL * fkeys + FD_WG - 1 ) / FD_WG );
+  /* with key_full = 2 a claim builds all 32 P_j (32 lanes per key) and all four groups of tables; the slots
+     promoted in this batch (at most pmax, the count on the device) build three groups each in fd_ftab_kernel */
+  unsigned lpk = kf && ctx->kfull_mode == 2 ? 32u : 8u, cg = lpk / 8u;
+  unsigned long pkeys = fkeys ? ctx->pmax : 0UL;
+  unsigned fbk = (unsigned)( ( lpk * fkeys + FD_WG - 1 ) / FD_WG );
   hipLaunchKernelGGL( ( ks ? fd_hashh_kernel<1> : fd_hashh_kernel<0> ), dim3( ks ? hb + fbk + sg + ( kf ? 2 : 1 ) : sg ),
                       dim3(FD_WG), 0, st,
                       b.d_payload, b.d_desc, ctx->d_map, nsig, ctx->semantics, ctx->d_pstat, code, ctx->d_digA, ctx->d_digR,
@@ -3476,11 +3616,11 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       (u32 const *)( ks ? ctx->d_hlist : NULL ), (uint4 const *)( ks ? ctx->d_Axy : NULL ),
                       ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb, (u32 const *)( kf ? ctx->d_orderh : NULL ),
                       (u32 const *)( kf ? ctx->d_flist : NULL ), kf ? ctx->d_fbase : (uint4 *)NULL, (u32)fbk,
-                      kf ? ctx->d_sstat : (unsigned char *)NULL, kf ? ctx->d_Rxy : (uint4 *)NULL );
+                      kf ? ctx->d_sstat : (unsigned char *)NULL, kf ? ctx->d_Rxy : (uint4 *)NULL, (u32)lpk );
   if( fkeys )
-    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( fkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt,
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( cg * fkeys + 3UL * pkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt,
                         (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_astat, (uint4 const *)ctx->d_fbase,
-                        ctx->d_ftab );
+                        ctx->d_ftab, (u32)cg, (u32 const *)ctx->d_plist, ctx->pmax );
   if( ctx->timing ) hipEventRecord( b.ev[1], st );
   /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the rest (if any) in
      fd_dsm_slow_kernel */
@@ -3493,7 +3633,8 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       ctx->d_pstat, ctx->d_htop, 0, ctx->semantics, arep, order, kscnt, hidx,
                       (uint4 const *)( ks ? ctx->d_htab : NULL ), (uint4 const *)( ks ? ctx->d_btabh : NULL ),
                       (u32 const *)( kf ? ctx->d_fidx : NULL ), (uint4 const *)( kf ? ctx->d_ftab : NULL ),
-                      (uint4 const *)( kf ? ctx->d_btabf : NULL ), kf ? ctx->d_P : (u32 *)NULL );
+                      (uint4 const *)( kf ? ctx->d_btabf : NULL ), kf ? ctx->d_P : (u32 *)NULL,
+                      (u32 const *)( kf ? ctx->d_sfull : NULL ), kf ? slow_word( ctx, FD_SW_HOT ) + FD_KC_FFS : (u32 *)NULL );
   if( ctx->timing ) hipEventRecord( b.ev[2], st );
   if( fkeys ) {
     /* the fixed-base signatures' R, compared undecoded: the full-length path's chain over the fixed-base segment of
@@ -3523,7 +3664,7 @@ static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   hipLaunchKernelGGL( fd_decode_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig, 0,
                       ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
                       (u32 *)NULL, (unsigned char *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL,
-                      (u32 const *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, 0u );
+                      (u32 const *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, 0u, (u32 const *)NULL );
   hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig,
                       ctx->semantics, 1, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
                       (uint4 const *)ctx->d_khash );
@@ -3574,14 +3715,14 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
 fdgpu_debug_set_opts( fdgpu_debug_opts_t const * opts ) {
   std::lock_guard<std::mutex> lk( g_dbg_mu );
   if( opts ) g_dbg = *opts;
-  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+  else       g_dbg = fdgpu_debug_opts_t{ -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 }
 
 /* staging + device buffers of async slot i (once) */
@@ -3675,6 +3816,9 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
         u32 iw = 8u;
         if( ctx->kc_mode != 2 ) while( iw < 4u * ctx->fb_cap ) iw <<= 1;
         ctx->kc_iwords = iw; ctx->kc_iprobes = ctx->kc_mode == 2 ? 2u : FD_KD_PROBES;
+        /* full slots: a batch promotes at most a quarter of the slots, which bounds its one-off cost */
+        ctx->kfull_mode = dbg.key_full;
+        ctx->pmax = ctx->kfull_mode == 1 ? 0u : ctx->fb_cap / 4u > 1u ? ctx->fb_cap / 4u : 1u;
       }
       HIPCHK( ctx_dev_alloc( ctx, &ctx->d_kidx, ( (size_t)ctx->kc_iwords + slots ) * sizeof(u32) ), -1 );   /* (cleared per batch, */
       ctx->d_ktab = ctx->d_kidx + ctx->kc_iwords;                                                        /*  launch_half) */
@@ -3701,15 +3845,16 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fidx, ns * sizeof(u32) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_flist, fcn * 2 * sizeof(u32) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_skey, fcn * 8 * sizeof(u32) ), -1 );
-          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sstate, fcn * 2 * sizeof(u32) ), -1 );
-          ctx->d_sbirth = ctx->d_sstate + fcn;
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sstate, fcn * 3 * sizeof(u32) ), -1 );
+          ctx->d_sbirth = ctx->d_sstate + fcn; ctx->d_sfull = ctx->d_sbirth + fcn;
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_plist, ( ctx->pmax ? ctx->pmax : 1UL ) * sizeof(u32) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sstat, fcn ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_mlist, ( ns / ctx->fb_min + 1UL ) * sizeof(u32) ), -1 );
-          HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, fcn * 2 * sizeof(u32), ctx->stream ), -1 );   /* every slot empty */
+          HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, fcn * 3 * sizeof(u32), ctx->stream ), -1 );   /* every slot empty */
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_orderh, ns * sizeof(u32) ), -1 );
-          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fbase, fcn * FD_FB_T * 8 * sizeof(uint4) ), -1 );
-          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ftab, fcn * FD_FB_T * FD_FB_E * 6 * sizeof(uint4) ), -1 );
-          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabf, (size_t)FD_FB_T * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fbase, fcn * FD_FB_NT * 8 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ftab, fcn * FD_FB_NT * FD_FB_E * 6 * sizeof(uint4) ), -1 );
+          HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabf, (size_t)FD_FB_NB * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fslow, ns * sizeof(u32) ), -1 );
         }
       }
@@ -3736,9 +3881,9 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
                           ctx->d_btabh + (size_t)t * FD_BTAB_ENTRIES * 6, e[t] );
   }
   if( ctx->key_fixed )
-    for( int t=0; t<FD_FB_T; t++ )
+    for( int u=0; u<FD_FB_NB; u++ )                    /* (the walk with doublings reads the even ones) */
       hipLaunchKernelGGL( fd_btab_kernel, dim3((FD_BTAB_ENTRIES + 255)/256), dim3(256), 0, ctx->stream,
-                          ctx->d_btabf + (size_t)t * FD_BTAB_ENTRIES * 6, 32*t );
+                          ctx->d_btabf + (size_t)u * FD_BTAB_ENTRIES * 6, 16*u );
   HIPCHK( hipGetLastError(), -1 );
   for( int i=0; i<FD_NSLOT; i++ ) HIPCHK( hipEventCreateWithFlags( &ctx->slot[i].done, hipEventDisableTiming ), -1 );
   HIPCHK( ctx_pin_alloc( ctx, &ctx->h_flag, ( FD_NSLOT + 2 ) * sizeof(unsigned long), &ctx->d_flag ), -1 );
@@ -5251,6 +5396,19 @@ fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, uns
   if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_HIT, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
   if( hits ) *hits = (unsigned long)cnt[0];
   if( builds ) *builds = (unsigned long)cnt[2];
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs ) {
+  if( keys ) *keys = 0UL;
+  if( sigs ) *sigs = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_fixed || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 2 ] = { 0u, 0u };
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_FFK, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( keys ) *keys = (unsigned long)cnt[0];
+  if( sigs ) *sigs = (unsigned long)cnt[1];
   return 0;
 }
 

@@ -388,3 +388,28 @@ FD_LAT_FN int fd_fb_recode( signed char d[ 32 ], uint32_t const k[ 8 ] ) {
   }
   return carry;
 }
+
+/* The two fixed-base walks' schedules, as index arithmetic that the kernels and the host tests share.
+   A key's slot holds FD_FB_NT = 32 tables, table j = { [e]([2^(8j)](-A)) : e = 1..128 }, and the base point has
+   FD_FB_NB = 16, table u = { [e]([2^(16u)]B) : e = 0..32768 }; digit a_j of k (fd_fb_recode) has weight 2^(8j) and digit
+   b_i of S weight 2^(16i).  Entry |digit| is read and negated for a negative digit; entry 0 is the identity.
+
+   The body with doublings (dsmf_one) runs four steps r = 3, 2, 1, 0 with 8 doublings between them.  Step r makes
+   fd_fb_old_adds( r ) additions: number i < 8 is digit a_(4i+r) from the key's table 4i, and in the even steps
+   number i >= 8 is digit b_(2(i-8)+(r>>1)) from the base point's table 2(i-8).  Those are the slot's tables
+   j = 0 (mod 4) and the base point's even ones: what the step's place in the doublings contributes, 2^(8r), times
+   the table's own 2^(32t).
+
+   The body without doublings (dsmf_full) makes FD_FB_FULL_ADDS = 48 additions: number i is digit a_(2(i/3)+(i%3))
+   from the key's table of the same number when i % 3 < 2, else digit b_(i/3) from the base point's table i/3. */
+#define FD_FB_NT        32
+#define FD_FB_NB        16
+#define FD_FB_FULL_ADDS 48
+FD_LAT_FN int fd_fb_entry( int d ) { return d < 0 ? -d : d; }
+FD_LAT_FN int fd_fb_old_adds( int r ) { return ( r & 1 ) ? 8 : 16; }
+FD_LAT_FN int fd_fb_old_is_base( int i ) { return i >= 8; }
+FD_LAT_FN int fd_fb_old_digit( int r, int i ) { return i < 8 ? 4*i + r : 2*( i - 8 ) + ( r >> 1 ); }
+FD_LAT_FN int fd_fb_old_table( int i ) { return i < 8 ? 4*i : 2*( i - 8 ); }
+FD_LAT_FN int fd_fb_full_is_base( int i ) { return ( i % 3 ) == 2; }
+FD_LAT_FN int fd_fb_full_digit( int i ) { return ( i % 3 ) == 2 ? i / 3 : 2*( i / 3 ) + ( i % 3 ); }
+FD_LAT_FN int fd_fb_full_table( int i ) { return fd_fb_full_digit( i ); }

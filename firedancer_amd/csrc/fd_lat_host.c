@@ -28,3 +28,24 @@ int
 fd_fb_recode_host( signed char d[ 32 ], uint32_t const k[ 8 ] ) {
   return fd_fb_recode( d, k );
 }
+
+/* the two fixed-base walks' schedules (tests/test_fb_full_schedule.py): out[0] = additions of old step r, then per
+   addition (is_base, digit, table); likewise the body without doublings */
+int
+fd_fb_old_sched_host( int r, int * out ) {
+  int na = fd_fb_old_adds( r );
+  for( int i=0; i<na; i++ ) { out[3*i] = fd_fb_old_is_base( i ); out[3*i+1] = fd_fb_old_digit( r, i ); out[3*i+2] = fd_fb_old_table( i ); }
+  return na;
+}
+
+int
+fd_fb_full_sched_host( int * out ) {
+  for( int i=0; i<FD_FB_FULL_ADDS; i++ ) { out[3*i] = fd_fb_full_is_base( i ); out[3*i+1] = fd_fb_full_digit( i ); out[3*i+2] = fd_fb_full_table( i ); }
+  return FD_FB_FULL_ADDS;
+}
+
+int
+fd_fb_entry_host( int d ) { return fd_fb_entry( d ); }
+
+int
+fd_fb_tables_host( int * nt, int * nb ) { *nt = FD_FB_NT; *nb = FD_FB_NB; return 0; }

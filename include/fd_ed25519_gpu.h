@@ -429,6 +429,22 @@ fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys
 int
 fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, unsigned long * builds );
 
+/* Full slots in the last batch launched on ctx.  A slot of the key cache
+   has room for 32 tables, one per byte of k (384 KB; with the 4,096 slots
+   of a context of a million signatures that is 1.5 GiB of device memory,
+   allocated with the context).  The batch that claims a slot builds 8 of
+   them, and its signatures walk 24 doublings.  A key found resident in a
+   later batch is promoted (at most a quarter of the slots per batch): the
+   other 24 tables are built once, and from then on a wave whose lanes all
+   have such a key adds 48 table entries and doubles nothing.  *keys = the
+   batch's fixed-base keys whose slot was full at the walk, *sigs = the
+   signatures that walked that way (a wave that holds one signature of a
+   key not yet promoted walks with doublings, and counts none).  Both 0
+   when fixed_count's are, or with fdgpu_debug_opts_t.key_full = 1.  Waits
+   for the batch; 0 on success. */
+int
+fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs );
+
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
                     unsigned long *       out_tags,
@@ -789,6 +805,11 @@ typedef struct fdgpu_debug_opts {
                                         every slot is emptied ahead of each batch, so every key builds its tables (A/B:
                                         the same kernels and launches); 2 = TESTS, 8 slots and an 8-word index with two
                                         probes, so a few keys evict each other and some residents cannot be found */
+  int           key_full;            /* half-size throughput path with key_fixed on: 0 = default, a fixed-base key found
+                                        resident in a later batch is promoted: its slot gets a table for every byte of k
+                                        and its signatures walk no doubling (fdgpu_ed25519_ffull_count); 1 = off, no slot
+                                        is ever promoted (A/B: the walk with 24 doublings for every key); 2 = TESTS, a
+                                        claim fills its slot at once, so a single batch on a fresh context walks that way */
 } fdgpu_debug_opts_t;
 
 void
