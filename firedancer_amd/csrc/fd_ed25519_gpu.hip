@@ -61,6 +61,7 @@
 #include "fd_gpu_curve.h"
 #include "fd_gpu_txn.h"
 #include "fd_gpu_lattice.h"
+#include "fd_pin_list.h"
 #include "../../include/fd_ed25519_gpu.h"
 
 #include <hip/hip_runtime.h>
@@ -259,6 +260,10 @@ FD_DEV u32 ks_sig( u32 const * __restrict__ order, u32 const * __restrict__ orde
 #define FD_KC_PTIX  11
 #define FD_KC_FFK   12
 #define FD_KC_FFS   13
+/* ... and the pinned keys' (DESIGN 19): the representatives whose key was found in a pinned slot, and the signatures
+   that are fixed-base because of it */
+#define FD_KC_PINK  14
+#define FD_KC_PINS  15
 
 /* ------------------------------------------------------------------ */
 
@@ -2591,6 +2596,8 @@ struct fd_kcache {
   u32 *           plist;     /* [pmax] the slots promoted in this batch */
   u32             pmax;      /* the most slots a batch promotes (0: none, fdgpu_debug_opts_t.key_full = 1) */
   u32             fnow;      /* a claim builds all 32 tables at once (fdgpu_debug_opts_t.key_full = 2) */
+  /* pinned keys */
+  u32             npin;      /* slots [0, npin) hold the keys fdgpu_ed25519_set_pinned_keys named: full, never claimed */
 };
 
 template<int KS>
@@ -2624,6 +2631,10 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
   __shared__ u32 wcnt[ FD_WG / 64 + 1 ];
   if( KS && blockIdx.x < iblk ) {
     u32 slot = blockIdx.x * FD_WG + threadIdx.x;
+    /* a pinned slot is stamped with this batch's number, so that fd_keyclaim_kernel's hand passes it as it
+       passes a hit, and gets its other two words back -- claimed in no batch, full -- in case launch_half's memset
+       has just emptied every slot: the key, the status and the tables are not in that memset */
+    if( slot < kc.npin ) { kc.state[slot] = kc.batch; kc.birth[slot] = 0u; kc.full[slot] = 1u; }
     if( slot >= kc.fcap || !kc.state[slot] ) return;
     u32 w[8];
 #pragma unroll
@@ -2639,7 +2650,7 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
     u32 * c = ucnt + 3;                                       /* (FD_KC_*: the three of the split, two of the fixed-base keys, */
     for( int k=0; k<5; k++ ) c[k] = 0u;                       /*  three of the key cache; the hand brought back below the slots */
     for( int k=FD_KC_HIT; k<=FD_KC_BUILD; k++ ) c[k] = 0u;    /*  so that a batch's draws never wrap, and its start noted; */
-    for( int k=FD_KC_PTIX; k<=FD_KC_FFS; k++ ) c[k] = 0u;     /*  three of the full slots) */
+    for( int k=FD_KC_PTIX; k<=FD_KC_PINS; k++ ) c[k] = 0u;    /*  three of the full slots, two of the pinned keys) */
     if( iblk ) { u32 h = c[FD_KC_HAND] % kc.fcap; c[FD_KC_HAND] = h; c[FD_KC_HAND0] = h; }
   }
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
@@ -2725,27 +2736,32 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
 __global__ void __launch_bounds__( FD_WG )
 fd_keysplit_kernel( u32 nsig, u32 const * __restrict__ arep, u32 const * __restrict__ kcnt, u32 hot_min,
                     u32 * __restrict__ hidx, u32 * __restrict__ hlist, u32 * __restrict__ order, u32 * __restrict__ cnt,
-                    u32 hcap, u32 const * __restrict__ fidx, u32 * __restrict__ orderh, u32 fb_min ) {
-  __shared__ u32 wc[ 4 ][ FD_WG / 64 ], base[ 4 ];
+                    u32 hcap, u32 const * __restrict__ fidx, u32 * __restrict__ orderh, u32 fb_min,
+                    /* pinned keys (npin = 0: none): the caller passes fb_min = 0, because fd_keyclass_kernel
+                       then wrote fidx[] for every representative and a key in a slot below npin is fixed-base
+                       whatever its count; cnt[FD_KC_PINS] counts those signatures */
+                    u32 npin ) {
+  __shared__ u32 wc[ 5 ][ FD_WG / 64 ], base[ 5 ];
   u32 s = blockIdx.x * FD_WG + threadIdx.x;
   int in = s < nsig;
   u32 rep = in ? arep[s] : 0u;
   u32 kc = in ? kcnt[rep] : 0u;
-  int fb  = fidx && kc >= fb_min && fidx[rep] != FD_FB_NONE;   /* (fidx[] is read, and was written, only for such keys) */
+  u32 fi = in && fidx && kc >= fb_min ? fidx[rep] : FD_FB_NONE;   /* (fidx[] is read, and was written, only for such keys) */
+  int fb  = fi != FD_FB_NONE;
   int hot = !fb && kc >= hot_min;
-  int f[ 4 ] = { hot && rep == s, hot, in && !hot && !fb, fb };
+  int f[ 5 ] = { hot && rep == s, hot, in && !hot && !fb, fb, fb && fi < npin };
   u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, rank[ 4 ];
 #pragma unroll
-  for( int k=0; k<4; k++ ) {
+  for( int k=0; k<5; k++ ) {
     unsigned long long mk = __ballot( f[k] );
     if( !lane ) wc[k][wv] = (u32)__popcll( mk );
-    rank[k] = (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) );
+    if( k < 4 ) rank[k] = (u32)__popcll( mk & ( ( 1ULL << lane ) - 1ULL ) );
   }
   __syncthreads();
-  if( threadIdx.x < 4u ) {
+  if( threadIdx.x < 5u ) {
     u32 k = threadIdx.x, tot = 0u;
     for( u32 w=0; w<FD_WG/64; w++ ) { u32 c = wc[k][w]; wc[k][w] = tot; tot += c; }
-    base[k] = tot ? atomicAdd( cnt + ( k < 3u ? k : (u32)FD_KC_FB ), tot ) : 0u;
+    base[k] = tot ? atomicAdd( cnt + ( k < 3u ? k : k == 3u ? (u32)FD_KC_FB : (u32)FD_KC_PINS ), tot ) : 0u;
   }
   __syncthreads();
   if( f[0] ) { u32 i = base[0] + wc[0][wv] + rank[0]; if( i < hcap ) { hidx[s] = i; hlist[i] = s; } }
@@ -2765,30 +2781,52 @@ fd_keysplit_kernel( u32 nsig, u32 const * __restrict__ arep, u32 const * __restr
            nsig / fb_min of them) for fd_keyclaim_kernel.
    fidx[rep] is written for these representatives alone: fd_keysplit_kernel reads it only where the count reached
    fb_min too.  A launch of its own, because fd_keysplit_kernel's lanes read their representative's class.  A
-   batch the de-duplication only sampled (ucnt[1] set) counted nothing: no lane of this kernel does anything. */
+   batch the de-duplication only sampled (ucnt[1] set) counted nothing: no lane of this kernel does anything.
+   With pinned keys (kc.npin != 0) every representative looks its key up, in a sampled batch too, and
+   fidx[rep] is written for every one of them: a key found in a slot below npin is fixed-base whatever its count. */
 __global__ void __launch_bounds__( FD_WG )
 fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucnt, u32 const * __restrict__ kcnt,
                     u32 fb_min, u32 * __restrict__ fidx, u32 * __restrict__ mlist, u32 * __restrict__ cnt,
                     unsigned char const * __restrict__ payload, fdgpu_txn_desc_t const * __restrict__ desc,
                     u32 const * __restrict__ map, u32 seed32, unsigned char * __restrict__ astat, fd_kcache kc ) {
   u32 i = blockIdx.x * FD_WG + threadIdx.x;
-  if( ucnt[1] || i >= ucnt[0] ) return;
+  int sampled = ucnt[1] != 0u;
+  if( ( sampled && !kc.npin ) || i >= ucnt[0] ) return;
   u32 s = ulist[i];
-  if( kcnt[s] < fb_min ) return;
+  int bound = !sampled && kcnt[s] >= fb_min;
+  if( !bound && !kc.npin ) return;
   u32 m = map[s];
   fdgpu_txn_desc_t d = desc[m & 0xffffffu];
+  /* (with pins every representative comes this far, also a malformed transaction's, whose acct_addr_off may point
+     outside the payload: it loads no key.  One at the bound is well-formed: the de-duplication counted it) */
+  if( kc.npin && !txn_desc_ok( d ) ) { fidx[s] = FD_FB_NONE; return; }
   u32 w[8];
   fd_load_words<8>( w, payload + d.payload_off + (u32)d.acct_addr_off + 32u*( m >> 24 ) );
   u32 h = (u32)( fd_key_hash( w, seed32 ) >> 32 );
+  u32 slot = FD_FB_NONE;
   for( u32 p=0; p<kc.iprobes; p++ ) {
     u32 v = kc.idx[ ( h + p ) & kc.imask ];
     if( !v ) break;                                  /* (no insert after the launch before: an empty word ends the search) */
-    u32 slot = v - 1u;
-    if( slot >= kc.fcap ) continue;
+    u32 sl = v - 1u;
+    if( sl >= kc.fcap ) continue;
     u32 diff = 0u;
 #pragma unroll
-    for( int k=0; k<8; k++ ) diff |= w[k] ^ kc.key[ 8u*slot + k ];
+    for( int k=0; k<8; k++ ) diff |= w[k] ^ kc.key[ 8u*sl + k ];
     if( diff ) continue;
+    if( sl < kc.npin ) {
+      /* a pinned key: fixed-base whatever its count, its slot full and already stamped by the index lanes;
+         it is no hit of the cache's count, promotes nothing and claims nothing */
+      fidx[s] = sl;
+      astat[s] = kc.stat[sl];
+      atomicAdd( cnt + FD_KC_FBK, 1u ); atomicAdd( cnt + FD_KC_PINK, 1u );
+      return;
+    }
+    slot = sl;
+    /* (with pins the search goes on past an unpinned slot of this key: should the key ever be resident twice -- a
+       batch whose index had no room for its pinned slot claimed another -- the pinned slot wins whenever it is found) */
+    if( !kc.npin ) break;
+  }
+  if( bound && slot != FD_FB_NONE ) {
     kc.state[slot] = kc.batch;
     fidx[s] = slot;
     u32 stt = kc.stat[slot];
@@ -2804,7 +2842,7 @@ fd_keyclass_kernel( u32 const * __restrict__ ulist, u32 const * __restrict__ ucn
     return;
   }
   fidx[s] = FD_FB_NONE;
-  mlist[ atomicAdd( cnt + FD_KC_MISS, 1u ) ] = s;
+  if( bound ) mlist[ atomicAdd( cnt + FD_KC_MISS, 1u ) ] = s;
 }
 
 /* The misses claim slots, one lane per miss; the grid holds min( nsig / fb_min, fb_cap ) lanes, blocks
@@ -2861,6 +2899,38 @@ fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 
     atomicAdd( cnt + FD_KC_FBK, 1u );
     return;
   }
+}
+
+/* Pinned keys: the build at fdgpu_ed25519_set_pinned_keys, outside any batch.  The host has written the m
+   distinct keys of its list to key[] of slots [0, m).  32 lanes per slot: lane (slot, j) decodes the key -- each of
+   the 32 for itself; a control-plane call once per epoch can afford 31 decodes that a scratch row of affine points
+   would save -- and, if it decodes and is not of small order, stores P_j = [2^(8j)](-A), as fbase_build does from the
+   same canonical affine point.  Lane j = 0 records the status (rc | small_order << 2, as decode_one) and lists
+   (slot, slot) in flist[], so that fd_ftab_kernel, launched next with cg = 4, the slots' status as its astat[] and
+   pcnt[] as its counters, builds all 32 tables of every slot. */
+__global__ void __launch_bounds__( FD_WG )
+fd_keypin_kernel( u32 m, u32 const * __restrict__ key, unsigned char * __restrict__ sstat, uint4 * __restrict__ fbase,
+                  u32 * __restrict__ flist, u32 * __restrict__ pcnt ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( !i ) { pcnt[FD_KC_BUILD] = m; pcnt[FD_KC_PTIX] = 0u; }
+  u32 slot = i / (u32)FD_FB_NT, j = i % (u32)FD_FB_NT;
+  if( slot >= m ) return;
+  u32 w[8];
+#pragma unroll
+  for( int k=0; k<8; k++ ) w[k] = key[ 8u*slot + k ];
+  ge_p3 P; int rc;
+  ge_decode1( P, rc, w );
+  u32 st = (u32)rc | ( (u32)ge_affine_is_small_order( P ) << 2 );
+  if( !j ) { sstat[slot] = (unsigned char)st; flist[2u*slot] = slot; flist[2u*slot+1u] = slot; }
+  if( st & 7u ) return;
+  u32 x[8], y[8];
+  fe_pack( x, P.X ); fe_pack( y, P.Y );
+  ge_p3 A;
+  fe_unpack( A.X, x ); fe_unpack( A.Y, y );
+  A.Z = fe_one();
+  fe_neg( A.X, A.X ); fe_wcarry( A.X, A.X );              /* -A */
+  fe_mul( A.T, A.X, A.Y );
+  fbase_chain( fbase, slot, j, A, 8*(int)j );
 }
 
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
@@ -3237,6 +3307,8 @@ struct fdgpu_ed25519_ctx {
                                       its slot at once) */
   u32     pmax;                  /*   max( 1, fb_cap / 4 ): the most slots one batch promotes; 0 with key_full off */
   u32 *   d_plist;               /*   [pmax] the slots promoted in this batch */
+  u32     npin;                  /*   pinned keys (fdgpu_ed25519_set_pinned_keys): slots [0, npin) are theirs, built full
+                                      at that call, stamped by every batch and so never claimed; 0: none */
   unsigned char * d_sstat;       /*   [fb_cap] the key's decode status */
   u32 *   d_mlist;               /*   [max_sig / fb_min + 1] the representatives of this batch's misses */
   u32 *   d_orderh;              /*   [max_sig] the hot signatures as the split lists them (ks_sig) */
@@ -3540,6 +3612,11 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
      of fd_keyclaim_kernel, of fbase_build's blocks and of fd_ftab_kernel */
   unsigned long fkeys = kf ? nsig / ctx->fb_min : 0UL; if( fkeys > ctx->fb_cap ) fkeys = ctx->fb_cap;
   fd_kcache kc = {}; unsigned iblk = 0u;
+  /* pinned keys: fd_keyclass_kernel gives every representative a class, so the kernels that read fidx[] only
+     where the key's count reached the bound read it everywhere (their bound is 0), and the R-check chain behind the
+     walk runs whatever nsig is: a batch of one signature can be fixed-base.  Without pins (npin = 0) every
+     argument and every launch is as before */
+  u32 npin = kf ? ctx->npin : 0u, fbm = npin ? 0u : ctx->fb_min;
   if( kd ) {
     /* the table cleared for this batch -- the smallest power of two of slots that is twice its signatures, so a
        small batch on a large context clears little -- then (ks) the signatures per key counted and the batch
@@ -3555,6 +3632,7 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
       if( !++ctx->kc_batch ) { ctx->kc_batch = 1u; ctx->kc_dirty = 1; }        /* (the number wrapped: old stamps mean nothing) */
       kc.batch = ctx->kc_batch;
       kc.full = ctx->d_sfull; kc.plist = ctx->d_plist; kc.pmax = ctx->pmax; kc.fnow = ctx->kfull_mode == 2;
+      kc.npin = ctx->npin;
       int clear = ctx->kc_mode == 1 || ctx->kc_dirty;
       ctx->kc_dirty = 2;                                   /* (until launch_batch has launched all of this batch) */
       if( clear ) HIPCHK( hipMemsetAsync( ctx->d_sstate, 0, ( ctx->fb_cap ? ctx->fb_cap : 1UL ) * 3 * sizeof(u32), st ), -3 );   /* (state, birth, full) */
@@ -3584,7 +3662,7 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
       hipLaunchKernelGGL( fd_keysplit_kernel, dim3(sg), dim3(FD_WG), 0, st, nsig, (u32 const *)ctx->d_arep,
                           (u32 const *)ctx->d_kcnt, ctx->hot_min, ctx->d_hidx, ctx->d_hlist, ctx->d_order,
                           slow_word( ctx, FD_SW_HOT ), ctx->hot_cap, (u32 const *)( kf ? ctx->d_fidx : NULL ),
-                          kf ? ctx->d_orderh : (u32 *)NULL, kf ? ctx->fb_min : 0u );
+                          kf ? ctx->d_orderh : (u32 *)NULL, kf ? fbm : 0u, npin );
   }
   /* kd: A lanes over the representatives in the first sg blocks, R lanes over every signature; else lanes 2s, 2s+1 */
   /* kf: the R lanes by place in the partition (sg + 2 blocks at most), none for the fixed-base signatures */
@@ -3594,7 +3672,7 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       kd ? (u32 const *)ctx->d_ulist : NULL, kd ? ucnt : (u32 *)NULL,
                       kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u, kf ? order : (u32 const *)NULL,
                       (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL,
-                      (u32 const *)( kf ? ctx->d_kcnt : NULL ), kf ? ctx->fb_min : 0u, (u32 const *)( kf ? ctx->d_fidx : NULL ),
+                      (u32 const *)( kf ? ctx->d_kcnt : NULL ), kf ? fbm : 0u, (u32 const *)( kf ? ctx->d_fidx : NULL ),
                       (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch, (u32 const *)( kf ? ctx->d_sfull : NULL ) );
   if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
   /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
@@ -3636,7 +3714,7 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       (uint4 const *)( kf ? ctx->d_btabf : NULL ), kf ? ctx->d_P : (u32 *)NULL,
                       (u32 const *)( kf ? ctx->d_sfull : NULL ), kf ? slow_word( ctx, FD_SW_HOT ) + FD_KC_FFS : (u32 *)NULL );
   if( ctx->timing ) hipEventRecord( b.ev[2], st );
-  if( fkeys ) {
+  if( fkeys || npin ) {
     /* the fixed-base signatures' R, compared undecoded: the full-length path's chain over the fixed-base segment of
        order[] (the worst case of blocks; those beyond the device-side count return at once), with a list and a
        counter of its own -- fd_dsm_slow_kernel below still reads the half-size slow list's */
@@ -5409,6 +5487,64 @@ fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsi
   if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_FFK, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
   if( keys ) *keys = (unsigned long)cnt[0];
   if( sigs ) *sigs = (unsigned long)cnt[1];
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_pinned_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs ) {
+  if( keys ) *keys = 0UL;
+  if( sigs ) *sigs = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_fixed || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 2 ] = { 0u, 0u };
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_PINK, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( keys ) *keys = (unsigned long)cnt[0];
+  if( sigs ) *sigs = (unsigned long)cnt[1];
+  return 0;
+}
+
+extern "C" unsigned long
+fdgpu_ed25519_pin_cap( fdgpu_ed25519_ctx_t * ctx ) {
+  if( !ctx || !ctx->half || !ctx->key_fixed ) return 0UL;
+  return fd_pin_list_cap( ctx->fb_cap );
+}
+
+/* Pinned keys.  The list is de-duplicated on the host (fd_pin_list.h); distinct key number j takes slot
+   j.  Marking the cache dirty makes the next batch empty every slot before anything else (launch_half), after which
+   its index lanes restore slots [0, npin): that is the emptying of every unpinned slot, and, should the build below
+   fail, of the half-built ones too (npin is then 0).  The build: the keys into d_skey, fd_keypin_kernel (status,
+   the 32 P_j), fd_ftab_kernel over all four groups of every slot, with its counters in words of d_Rxy, which no
+   batch is using -- the batch's own counters stay the last batch's. */
+extern "C" int
+fdgpu_ed25519_set_pinned_keys( fdgpu_ed25519_ctx_t * ctx, unsigned char const * keys, unsigned long n,
+                               unsigned char * status_out ) {
+  if( !ctx || ( n && !keys ) ) { fd_err = "fdgpu_ed25519_set_pinned_keys: bad arguments"; return -1; }
+  if( n > fdgpu_ed25519_pin_cap( ctx ) ) { fd_err = "fdgpu_ed25519_set_pinned_keys: more keys than fdgpu_ed25519_pin_cap"; return -1; }
+  if( async_busy( ctx ) ) { fd_err = "fdgpu_ed25519_set_pinned_keys: the async pipeline holds a batch"; return -2; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_set_pinned_keys: the context is faulted"; return -3; }
+  if( !ctx->key_fixed ) return 0;                        /* (n = 0 on a context that cannot pin) */
+  std::vector<unsigned int> slot_of( n ? n : 1UL ), first_of( n ? n : 1UL ), work( fd_pin_list_work( n ) );
+  unsigned long m = fd_pin_list_dedup( keys, n, slot_of.data(), first_of.data(), work.data() );
+  std::vector<unsigned char> uniq( 32UL * ( m ? m : 1UL ) ), st( m ? m : 1UL );
+  for( unsigned long j=0UL; j<m; j++ ) memcpy( uniq.data() + 32UL*j, keys + 32UL*first_of[j], 32UL );
+  HIPCHK( hipSetDevice( ctx->device ), -3 );
+  HIPCHK( hipStreamSynchronize( ctx->stream ), -3 );
+  ctx->npin = 0u; ctx->kc_dirty = 1;
+  if( m ) {
+    hipStream_t s = ctx->stream;
+    u32 * pcnt = (u32 *)ctx->d_Rxy;
+    HIPCHK( hipMemcpy( ctx->d_skey, uniq.data(), 32UL*m, hipMemcpyHostToDevice ), -3 );
+    hipLaunchKernelGGL( fd_keypin_kernel, dim3( (unsigned)( ( (unsigned long)FD_FB_NT * m + FD_WG - 1UL ) / FD_WG ) ), dim3(FD_WG), 0, s,
+                        (u32)m, (u32 const *)ctx->d_skey, ctx->d_sstat, ctx->d_fbase, ctx->d_flist, pcnt );
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( 4UL * m + 1UL ) / 2UL ) ), dim3(FD_WG), 0, s, (u32 const *)pcnt,
+                        (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_sstat, (uint4 const *)ctx->d_fbase,
+                        ctx->d_ftab, 4u, (u32 const *)ctx->d_plist, 0u );
+    HIPCHK( hipGetLastError(), -3 );
+    HIPCHK( hipStreamSynchronize( s ), -3 );
+    HIPCHK( hipMemcpy( st.data(), ctx->d_sstat, m, hipMemcpyDeviceToHost ), -3 );
+  }
+  if( status_out ) for( unsigned long i=0UL; i<n; i++ ) status_out[i] = st[ slot_of[i] ];
+  ctx->npin = (u32)m;
   return 0;
 }
 

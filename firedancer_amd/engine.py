@@ -51,7 +51,7 @@ EXPORTS = ("fd_ed25519_verify", "fd_ed25519_verify_batch_single_msg", "fd_ed2551
            "fdgpu_ed25519_reserve_gather_cus", "fdgpu_ed25519_reserve_cus", "fdgpu_ed25519_set_cu_exclusive", "fdgpu_ed25519_get_cu_exclusive", "fdgpu_ed25519_set_lat_share", "fdgpu_ed25519_gather_stats", "fdgpu_ed25519_phase_stats", "fdgpu_ed25519_prepare", "fdgpu_ed25519_submit_raw_gather_dev", "fdgpu_host_region",
            "fdgpu_ed25519_dropin_init", "fdgpu_debug_set_opts", "fdgpu_debug_gather_pauses",
            "fdgpu_ed25519_pipeline_state", "fdgpu_ed25519_verify_many_host", "fdgpu_sha512_batch_device", "fdgpu_sha512_batch_host", "fdgpu_ed25519_set_timing", "fdgpu_ed25519_set_small_batch_max", "fdgpu_ed25519_kernel_ms", "fdgpu_mad_peak_per_s",
-           "fdgpu_ed25519_faulted", "fdgpu_ed25519_debug_fault", "fdgpu_ed25519_slow_count", "fdgpu_ed25519_key_count", "fdgpu_ed25519_hot_count", "fdgpu_ed25519_fixed_count", "fdgpu_ed25519_fcache_count", "fdgpu_ed25519_ffull_count", "fdgpu_ed25519_set_dedup",
+           "fdgpu_ed25519_faulted", "fdgpu_ed25519_debug_fault", "fdgpu_ed25519_slow_count", "fdgpu_ed25519_key_count", "fdgpu_ed25519_hot_count", "fdgpu_ed25519_fixed_count", "fdgpu_ed25519_fcache_count", "fdgpu_ed25519_ffull_count", "fdgpu_ed25519_set_pinned_keys", "fdgpu_ed25519_pin_cap", "fdgpu_ed25519_pinned_count", "fdgpu_ed25519_set_dedup",
            "fdgpu_ed25519_set_record_fp_off", "fdgpu_ed25519_batch_stats", "fdgpu_ed25519_launch_stats", "fdgpu_ed25519_front_remaining", "fdgpu_ed25519_front_batch", "fdgpu_ed25519_verify_txn_ptrs",
            "fdgpu_ed25519_submit_raw_gather_dev_f", "fdgpu_launcher_new", "fdgpu_launcher_delete", "fdgpu_launcher_stats", "fdgpu_ed25519_set_launcher",
            "fdgpu_ed25519_submit_raw_gather_to", "fdgpu_ed25519_set_dedup_seeds", "fdgpu_ed25519_debug_fail_launch",
@@ -160,6 +160,12 @@ def load_library():
         L.fdgpu_ed25519_fcache_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_ed25519_ffull_count.restype = ctypes.c_int
         L.fdgpu_ed25519_ffull_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_ed25519_set_pinned_keys.restype = ctypes.c_int
+        L.fdgpu_ed25519_set_pinned_keys.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p]
+        L.fdgpu_ed25519_pin_cap.restype = ctypes.c_ulong
+        L.fdgpu_ed25519_pin_cap.argtypes = [ctypes.c_void_p]
+        L.fdgpu_ed25519_pinned_count.restype = ctypes.c_int
+        L.fdgpu_ed25519_pinned_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_ed25519_submit_raw_ref.restype = ctypes.c_int
         L.fdgpu_ed25519_submit_raw_ref.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ushort,
                                                    ctypes.c_ulong]
@@ -505,7 +511,8 @@ class Engine:
 
     def fixed_count(self) -> tuple[int, int]:
         """(fixed-base keys, their signatures) of the last batch: those of hot_count() whose key got tables of
-        its own and that walked 24 doublings (0, 0 elsewhere)."""
+        its own and that walked 24 doublings, and those of pinned keys: hits + builds of fcache_count() + the
+        representatives of pinned_count() (0, 0 elsewhere)."""
         k, s = ctypes.c_ulong(), ctypes.c_ulong()
         if self.L.fdgpu_ed25519_fixed_count(self.ctx, ctypes.byref(k), ctypes.byref(s)):
             raise RuntimeError("fdgpu_ed25519_fixed_count: " + last_error())
@@ -513,7 +520,7 @@ class Engine:
 
     def fcache_count(self) -> tuple[int, int]:
         """(hits, builds) of the last batch: its fixed-base keys whose tables the context still held, and those
-        that built them in this batch (0, 0 elsewhere)."""
+        that built them in this batch; pinned keys are neither (0, 0 elsewhere)."""
         h, b = ctypes.c_ulong(), ctypes.c_ulong()
         if self.L.fdgpu_ed25519_fcache_count(self.ctx, ctypes.byref(h), ctypes.byref(b)):
             raise RuntimeError("fdgpu_ed25519_fcache_count: " + last_error())
@@ -525,6 +532,33 @@ class Engine:
         k, s = ctypes.c_ulong(), ctypes.c_ulong()
         if self.L.fdgpu_ed25519_ffull_count(self.ctx, ctypes.byref(k), ctypes.byref(s)):
             raise RuntimeError("fdgpu_ed25519_ffull_count: " + last_error())
+        return int(k.value), int(s.value)
+
+    def set_pinned_keys(self, keys) -> np.ndarray:
+        """The context's pinned set becomes exactly keys (32-byte public keys; none unpins all): their signatures are
+        fixed-base in every later batch of the half-size throughput path, whatever their count in it
+        (fdgpu_ed25519_set_pinned_keys).  Synchronous.  Returns each key's decode status byte; raises on a
+        refusal, with the C return value as the exception's second argument."""
+        keys = [bytes(k) for k in keys]
+        if any(len(k) != 32 for k in keys):
+            raise ValueError("a public key has 32 bytes")
+        buf = np.frombuffer(b"".join(keys) + b"\0", np.uint8)
+        status = np.zeros(max(len(keys), 1), np.uint8)
+        rc = self.L.fdgpu_ed25519_set_pinned_keys(self.ctx, buf.ctypes.data, len(keys), status.ctypes.data)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_set_pinned_keys: {rc} {last_error()}", rc)
+        return status[:len(keys)]
+
+    def pin_cap(self) -> int:
+        """The most keys set_pinned_keys takes (0: the context has no fixed-base keys)."""
+        return int(self.L.fdgpu_ed25519_pin_cap(self.ctx))
+
+    def pinned_count(self) -> tuple[int, int]:
+        """(representatives found pinned, their signatures) of the last batch; part of fixed_count(), no part of
+        fcache_count() (0, 0 elsewhere)."""
+        k, s = ctypes.c_ulong(), ctypes.c_ulong()
+        if self.L.fdgpu_ed25519_pinned_count(self.ctx, ctypes.byref(k), ctypes.byref(s)):
+            raise RuntimeError("fdgpu_ed25519_pinned_count: " + last_error())
         return int(k.value), int(s.value)
 
     def poll(self, max_n: int = 4096, blocking: bool = False):

@@ -407,9 +407,13 @@ fdgpu_ed25519_hot_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hot_keys, un
    at least FD_FB_MIN (128) signatures in it that got tables of their own
    (at most 4,096 and at most max_sig / FD_FB_MIN per batch; a key beyond
    that stays hot), and the signatures of those keys, which walk 24
-   doublings.  Both 0 when that batch took
-   another path, was not de-duplicated in full, or the tables are off
-   (fdgpu_debug_opts_t.key_fixed).  Waits for the batch; 0 on success. */
+   doublings.  The representatives and signatures of pinned keys
+   (fdgpu_ed25519_pinned_count) are included, whatever their count in the
+   batch: fixed keys = the key cache's hits + its builds + the pinned
+   representatives.  Both 0 when that batch took
+   another path, was not de-duplicated in full and holds no pinned key, or
+   the tables are off (fdgpu_debug_opts_t.key_fixed).  Waits for the
+   batch; 0 on success. */
 int
 fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys, unsigned long * fixed_sigs );
 
@@ -418,7 +422,9 @@ fdgpu_ed25519_fixed_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * fixed_keys
    as a batch can have such keys: *hits = the batch's fixed-base keys whose
    tables were found resident (nothing decoded, nothing built for them),
    *builds = those that claimed a slot and built their tables in this
-   batch; together they are fixed_keys above.  Whether a key is fixed-base
+   batch; together with the representatives found pinned
+   (fdgpu_ed25519_pinned_count), which are neither, they are fixed_keys
+   above.  Whether a key that is not pinned is fixed-base
    in a batch is decided by that batch alone, as before.  A claim takes the
    next slot, round a hand, that this batch has not used; nothing is read
    back and nothing waits.  The cache is the context's: a context's batches
@@ -444,6 +450,63 @@ fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, uns
    for the batch; 0 on success. */
 int
 fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs );
+
+/* Pinned keys.  Whether a key is fixed-base is otherwise decided by each
+   batch alone: the batch must hold FD_FB_MIN (128) signatures of it.  A
+   caller that knows which keys will keep coming back a few dozen at a
+   time -- a validator knows the epoch's staked identities and authorized
+   voters -- names them here.  The pinned set of ctx becomes exactly
+   keys[0, 32 n); n = 0 unpins all.  Every distinct key of the list takes
+   one slot of the key cache (fdgpu_ed25519_fcache_count), which the
+   context allocated when it was created: 384 KB of tables per key, all 32
+   of them built by this call, never evicted.  From then on every
+   signature of a pinned key in a batch of the half-size throughput path
+   is fixed-base and walks without doublings, whatever the key's count in
+   the batch, down to a batch of one signature and also in a batch whose
+   keys were only sampled (fdgpu_ed25519_key_count).  The latency path
+   (batches of at most small_batch_max signatures) ignores pins: such a
+   batch ends with its slowest wave, so a mixed batch would gain nothing.
+
+   status_out (n bytes, or NULL): key i's decode status, rc | small_order
+   << 2 with rc 0 = decodes, 1 = not a point, 2 = x = 0 with the sign bit
+   set.  A key that does not decode or has small order is pinned too: it
+   builds no tables, and its signatures get their codes from the recorded
+   status.  A key listed twice is pinned once, and each of its entries
+   gets its status.
+
+   The call is synchronous: it waits for the context's stream, builds,
+   and waits again.  It also empties every unpinned slot of the key cache,
+   so that a pinned key is never resident twice; the keys that batches
+   find by themselves claim and build again as they come.  A control-plane
+   call, meant for once per epoch, with nothing in flight.
+
+   Returns 0 on success; -1 on bad arguments or n > fdgpu_ed25519_pin_cap
+   (the length of the list counts, duplicates included), and nothing
+   changes; -2 while the async pipeline has a batch filling or in flight,
+   and nothing changes; -3 if the context is faulted (nothing changes) or
+   the build failed (no key is pinned then). */
+int
+fdgpu_ed25519_set_pinned_keys( fdgpu_ed25519_ctx_t * ctx, unsigned char const * keys, unsigned long n,
+                               unsigned char * status_out );
+
+/* The most keys ctx can pin: three quarters of its key-cache slots
+   (min( max_sig / 128, 4096 ) of them: 3,072 pins for a context of
+   524,288 signatures or more, 768 for one of 131,072).  The last quarter
+   stays for the keys that batches find by themselves.  A pin costs no
+   memory beyond its slot, which the context already has.  0 when the
+   context has no fixed-base keys: half = 0, key_dedup, key_split or
+   key_fixed = 1, or half_force_slow set (fdgpu_debug_opts_t). */
+unsigned long
+fdgpu_ed25519_pin_cap( fdgpu_ed25519_ctx_t * ctx );
+
+/* Pinned keys in the last batch launched on ctx: *keys = the
+   representatives whose key was found pinned (one per distinct key,
+   unless the batch's keys were only sampled), *sigs = the signatures that
+   were fixed-base because of it.  Both are part of fixed_count's, and
+   neither a hit nor a build of fcache_count's.  Both 0 when that batch
+   took another path.  Waits for the batch; 0 on success. */
+int
+fdgpu_ed25519_pinned_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs );
 
 unsigned long
 fdgpu_ed25519_poll( fdgpu_ed25519_ctx_t * ctx,
