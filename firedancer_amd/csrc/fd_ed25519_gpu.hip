@@ -264,6 +264,10 @@ FD_DEV u32 ks_sig( u32 const * __restrict__ order, u32 const * __restrict__ orde
    that are fixed-base because of it */
 #define FD_KC_PINK  14
 #define FD_KC_PINS  15
+/* ... and the wide tables' (DESIGN 20): the fixed-base keys whose slot was wide at the walk, and the signatures that
+   walked 40 additions */
+#define FD_KC_FWK   16
+#define FD_KC_FWS   17
 
 /* ------------------------------------------------------------------ */
 
@@ -377,7 +381,9 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
                   u32                                   batch,
                   /* ... and counts the fixed-base keys whose slot is full (ucnt + 3 are the FD_KC_* words):
                      the classification and the claims are over, so full[] no longer changes in this batch */
-                  u32 const *              __restrict__ full ) {
+                  u32 const *              __restrict__ full,
+                  /* ... and those whose slot also has wide tables: a full slot below wcap */
+                  u32                                   wcap ) {
   u32 s, is_r;
   unsigned char * st;
   if( ulist ) {
@@ -400,6 +406,7 @@ fd_decode_kernel( unsigned char const *    __restrict__ payload,
       if( fidx && kcnt[s] >= fb_min ) {
         u32 slot = fidx[s];
         if( slot != FD_FB_NONE && full[slot] ) atomicAdd( ucnt + 3 + FD_KC_FFK, 1u );
+        if( slot < wcap && full[slot] ) atomicAdd( ucnt + 3 + FD_KC_FWK, 1u );   /* (FD_FB_NONE is no slot below wcap) */
         if( slot != FD_FB_NONE && birth[slot] != batch ) return;
       }
     } else if( order ) {
@@ -893,16 +900,35 @@ FD_DEV void hashf_one( unsigned char const * __restrict__ payload, fdgpu_txn_des
    claim runs one lane per (key, t) with j = 4t from the representative's canonical affine A (fbase_build), so the
    chain of up to 224 doublings is paid by 8 lanes of a key and not by the 1,024 that build its entries. */
 template<int FM = FD_CARRY_FOLD>
-FD_DEV void fbase_chain( uint4 * __restrict__ fbase, u32 fi, u32 j, ge_p3 & A, int nd ) {
+FD_DEV void chain_store( uint4 * __restrict__ b, ge_p3 & A, int nd ) {
 #pragma unroll 1
   for( int i=0; i<nd; i++ ) ge_p3_dbl<FM>( A, A );
   ge_cached c;
   ge_p3_to_cached<FM>( c, A );
-  uint4 * b = fbase + ( (size_t)fi * FD_FB_NT + j ) * 8;
   fe_store_packed( b + 0, c.YpX );
   fe_store_packed( b + 2, c.YmX );
   fe_store_packed( b + 4, c.Z   );
   fe_store_packed( b + 6, c.T2d );
+}
+template<int FM = FD_CARRY_FOLD>
+FD_DEV void fbase_chain( uint4 * __restrict__ fbase, u32 fi, u32 j, ge_p3 & A, int nd ) {
+  chain_store<FM>( fbase + ( (size_t)fi * FD_FB_NT + j ) * 8, A, nd );
+}
+/* (2X : 2Y : 2Z) of the point a cached entry (Y+X, Y-X, Z, 2dT) holds: all a doubling reads (no T) */
+FD_DEV void cached_to_dbl_input( ge_p3 & A, uint4 const * __restrict__ e ) {
+  fe ypx, ymx;
+  fe_from_quads( ypx, e[0], e[1] ); fe_from_quads( ymx, e[2], e[3] ); fe_from_quads( A.Z, e[4], e[5] );
+  fe_sub( A.X, ypx, ymx ); fe_wcarry( A.X, A.X );
+  fe_add( A.Y, ypx, ymx ); fe_wcarry( A.Y, A.Y );
+  fe_add( A.Z, A.Z, A.Z ); fe_wcarry( A.Z, A.Z ); A.T = fe_zero();
+}
+/* Wide tables: the 16 extra base points of slot fi, wbase[( 8 fi + t ) 2 + r - 1] = [2^(32t + 11r)](-A) for
+   r = 1, 2, by 11 r doublings from the slot's own P_4t; lane q = 2t + r - 1 of the slot's 16 */
+FD_DEV void wbase_chain( uint4 * __restrict__ wbase, uint4 const * __restrict__ fbase, u32 fi, u32 q ) {
+  u32 t = q >> 1, r = ( q & 1u ) + 1u;
+  ge_p3 A;
+  cached_to_dbl_input( A, fbase + ( (size_t)fi * FD_FB_NT + 4u*t ) * 8 );
+  chain_store( wbase + ( (size_t)fi * 16u + q ) * 8, A, 11*(int)r );
 }
 template<int FM = FD_CARRY_FOLD>
 FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 j, uint4 const * __restrict__ Axy, u32 rep ) {
@@ -919,10 +945,18 @@ FD_DEV void fbase_build( uint4 * __restrict__ fbase, u32 fi, u32 j, uint4 const 
 /* the identity in affine precomputed form (y+x = y-x = 1, 2dxy = 0), packed like a table entry: digit 0 */
 __device__ __attribute__(( aligned( 16 ) )) unsigned const fd_ptab_ident_w[ 24 ] = {
   1u,0u,0u,0u, 0u,0u,0u,0u,  1u,0u,0u,0u, 0u,0u,0u,0u,  0u,0u,0u,0u, 0u,0u,0u,0u };
+/* (the host's copy: the head of the wide tables' array) */
+static unsigned const fd_ptab_ident_host[ 24 ] = {
+  1u,0u,0u,0u, 0u,0u,0u,0u,  1u,0u,0u,0u, 0u,0u,0u,0u,  0u,0u,0u,0u, 0u,0u,0u,0u };
 
 /* entry e >= 1 of table j (of FD_FB_NT) of the key in slot fi: 6 uint4 (ypx, ymx, xy2d, canonical, packed 8x32) */
 FD_DEV size_t ftab_at( u32 fi, u32 j, u32 e ) {
   return ( ( (size_t)fi * FD_FB_NT + j ) * FD_FB_E + ( e - 1u ) ) * 6;
+}
+/* entry e >= 1 of wide table (t, r) of the key in slot fi, in the same format.  wtab[] begins with the
+   identity entry, so a zero digit reads offset 0 of the same array and the walk's gathers need no second base */
+FD_DEV size_t wtab_at( u32 fi, u32 t, u32 r, u32 e ) {
+  return ( ( (size_t)fi * 8u * FD_FB_WE + (size_t)fd_fb_wide_off( (int)t, (int)r ) ) + e ) * 6;
 }
 
 /* fd_ftab_kernel's two passes over a lane's eight points, written as recursions over the point's number so
@@ -972,32 +1006,60 @@ fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 const * __restrict__ flist,
                 /* a work item is (slot, group r), the 8 tables j = 4t + r of the slot.  Items [0, cg nk)
                    are the claims' groups 0..cg-1 (cg = 1; 4 with fdgpu_debug_opts_t.key_full = 2); the items after
                    them are groups 1..3 of the slots promoted in this batch (plist[], at most pmax) */
-                u32 cg, u32 const * __restrict__ plist, u32 pmax ) {
+                u32 cg, u32 const * __restrict__ plist, u32 pmax,
+                /* behind those, the wide tables of the slots below wcap: 24 items a slot, item q = 3t + r
+                   being the 128 lanes of wide table (t, r), lane g building entries 8g + 1 .. 8g + 8 -- first of the
+                   claims' slots when a claim fills its slot at once (wnow), then of the promoted slots' */
+                uint4 const * __restrict__ wbase, uint4 * __restrict__ wtab, u32 wcap, u32 wnow ) {
   u32 nk = kscnt[FD_KC_BUILD] * cg;                       /* the keys that claimed a slot in this batch */
   u32 np = kscnt[FD_KC_PTIX]; np = np < pmax ? np : pmax;
+  u32 nb = nk + 3u*np;                                    /* the items of the byte tables */
+  u32 nkw = wcap && wnow ? kscnt[FD_KC_BUILD] * 24u : 0u, nw = wcap ? nkw + 24u*np : 0u;
   u32 bi = blockIdx.x * 2u + ( threadIdx.x >> 7 );
-  if( blockIdx.x * 2u >= nk + 3u*np ) return;             /* (block-uniform) */
+  if( blockIdx.x * 2u >= nb + nw ) return;                /* (block-uniform) */
   /* a wave is of one item: lanes of an item that is beyond the count, or of a key without tables, skip the work
      together */
-  if( bi >= nk + 3u*np ) return;
-  u32 fi, grp;
-  if( bi < nk ) {
-    if( astat[ flist[ 2u*( bi / cg ) + 1u ] ] & 7u ) return;
-    fi = flist[ 2u*( bi / cg ) ]; grp = bi % cg;          /* its slot */
-  } else { fi = plist[ ( bi - nk ) / 3u ]; grp = ( bi - nk ) % 3u + 1u; }   /* (promoted: the slot has tables) */
-  u32 t = 4u*( ( threadIdx.x >> 4 ) & 7u ) + grp, g = threadIdx.x & 15u;
+  if( bi >= nb + nw ) return;
+  u32 fi, grp, t, g;
+  int top = 3;                                            /* the highest bit of g */
+  uint4 const * bp; uint4 * ent;
+  if( bi < nb ) {
+    if( bi < nk ) {
+      if( astat[ flist[ 2u*( bi / cg ) + 1u ] ] & 7u ) return;
+      fi = flist[ 2u*( bi / cg ) ]; grp = bi % cg;        /* its slot */
+    } else { fi = plist[ ( bi - nk ) / 3u ]; grp = ( bi - nk ) % 3u + 1u; }   /* (promoted: the slot has tables) */
+    t = 4u*( ( threadIdx.x >> 4 ) & 7u ) + grp; g = threadIdx.x & 15u;
+    bp = fbase + ( (size_t)fi * FD_FB_NT + t ) * 8;
+    ent = ftab + ftab_at( fi, t, 8u*g + 1u );
+  } else {
+    u32 wi = bi - nb, q;
+    if( wi < nkw ) {
+      if( astat[ flist[ 2u*( wi / 24u ) + 1u ] ] & 7u ) return;
+      fi = flist[ 2u*( wi / 24u ) ]; q = wi % 24u;
+    } else { fi = plist[ ( wi - nkw ) / 24u ]; q = ( wi - nkw ) % 24u; }
+    if( fi >= wcap ) return;                              /* (a slot without wide tables) */
+    t = q / 3u; u32 r = q % 3u;
+    /* a table of fewer than 1,024 entries: the lanes beyond it repeat its last lane's work, in step with it and
+       with the same values to the same addresses (they are lanes of the last lane's own wave: the tables' sizes are
+       multiples of 8 and the wave's first lane is always inside), so the wave's shuffles need no special case */
+    g = threadIdx.x & 127u;
+    u32 gl = (u32)fd_fb_wide_entries( (int)r ) / 8u - 1u; g = g < gl ? g : gl;
+    top = 6;
+    bp = r ? wbase + ( (size_t)fi * 16u + 2u*t + r - 1u ) * 8 : fbase + ( (size_t)fi * FD_FB_NT + 4u*t ) * 8;
+    ent = wtab + wtab_at( fi, t, r, 8u*g + 1u );
+  }
   int lane = (int)( threadIdx.x & 63u );
   ge_cached pc;
   {
-    atab_raw r; uint4 const * b = fbase + ( (size_t)fi * FD_FB_NT + t ) * 8;
+    atab_raw r;
 #pragma unroll
-    for( int i=0; i<8; i++ ) r.q[i] = b[i];
+    for( int i=0; i<8; i++ ) r.q[i] = bp[i];
     atab_unpack( pc, r );
   }
   ge_p3 Q; ge_p3_identity( Q );
   ge_p1p1 tt;
 #pragma unroll 1
-  for( int b=3; b>=0; b-- ) {                             /* [g]P_t */
+  for( int b=top; b>=0; b-- ) {                           /* [g]P_t */
     ge_p3_dbl( Q, Q );
     ge_add_cached( tt, Q, pc );
     ge_p3 Qa; ge_p1p1_to_p3( Qa, tt );
@@ -1009,7 +1071,6 @@ fd_ftab_kernel( u32 const * __restrict__ kscnt, u32 const * __restrict__ flist,
   /* pass 1: the eight points, projective, parked in their own entries (X, Y, Z: 96 B), and the prefix products
      of their Z */
   fe pf[ 8 ];
-  uint4 * ent = ftab + ftab_at( fi, t, 8u*g + 1u );
   ftab_pass1<0>( Q, pc, ent, pf );
   /* the inverse of the lane's product: the wave's prefix and suffix products of the lanes' products, the wave's
      total inverted, times the other lanes' product */
@@ -1499,6 +1560,45 @@ FD_DEV void dsmf_full( u32 col, size_t n, u32 fi, uint4 const * __restrict__ fta
   fe_store_planar( Pbuf + 20*n + col, n, P.Z );
 }
 
+/* The walk of a fixed-base signature whose key's slot has wide tables: every 32-bit span of k is three
+   digits of 11, 11 and 10 bits with a table each, so P is the sum of 24 + 16 entries.  Addition i reads what
+   fd_fb_wide_* say: per span the key's three tables, then the base point's two.  The three digits come from the four
+   bytes of the span that the hash role stored (fd_fb_wide_split); they are loaded again for each of the three
+   additions rather than kept, which costs loads that hit and no register.  Zero digits read the identity entry at
+   the head of wtab[], so every gather of the key's is wtab + an offset.  Gathered one addition ahead, two additions
+   a turn, P stored as dsmf_full does. */
+FD_DEV void wide_fetch( uint4 r[ 6 ], int & d, int i, size_t n, u32 fi, uint4 const * __restrict__ wtab,
+                        uint4 const * __restrict__ btabf, i8 const * __restrict__ dA, short const * __restrict__ dB ) {
+  if( !fd_fb_wide_is_base( i ) ) {
+    int t = fd_fb_wide_span( i ), q = fd_fb_wide_digit( i );
+    i8 const * p = dA + (size_t)( 4*t )*n;
+    d = fd_fb_wide_split( p[0], p[n], p[2*n], p[3*n], q );
+    ptab_fetch( r, wtab + ( d ? wtab_at( fi, (u32)t, (u32)q, (u32)fd_fb_entry( d ) ) : (size_t)0 ) );
+  } else {
+    d = dB[ (size_t)fd_fb_wide_digit( i )*n ];
+    ptab_fetch( r, btabf + ( (size_t)fd_fb_wide_table( i ) * FD_BTAB_ENTRIES + (size_t)fd_fb_entry( d ) ) * 6 );
+  }
+}
+template<int FM>
+FD_DEV void dsmf_wide( u32 col, size_t n, u32 fi, uint4 const * __restrict__ wtab, uint4 const * __restrict__ btabf,
+                       i8 const * __restrict__ digA, short const * __restrict__ digB, u32 * __restrict__ Pbuf ) {
+  ge_p3 P; ge_p3_identity( P );
+  i8 const * dA = digA + col; short const * dB = digB + col;
+  uint4 ra[ 6 ], rb[ 6 ];
+  int da, db;
+  wide_fetch( ra, da, 0, n, fi, wtab, btabf, dA, dB );
+#pragma unroll 1
+  for( int i=0; i<FD_FB_WIDE_ADDS; i+=2 ) {
+    wide_fetch( rb, db, i + 1, n, fi, wtab, btabf, dA, dB );
+    full_add<FM>( P, ra, da );
+    if( i + 2 < FD_FB_WIDE_ADDS ) wide_fetch( ra, da, i + 2, n, fi, wtab, btabf, dA, dB );
+    full_add<FM>( P, rb, db );
+  }
+  fe_store_planar( Pbuf + col, n, P.X );
+  fe_store_planar( Pbuf + 10*n + col, n, P.Y );
+  fe_store_planar( Pbuf + 20*n + col, n, P.Z );
+}
+
 template<int FM, int KS = 0>
 __global__ void __launch_bounds__( FD_WG, FM ? FD_DSMH_MINW : 1 )
 fd_dsmh_kernel( u32                      nsig,
@@ -1531,7 +1631,9 @@ fd_dsmh_kernel( u32                      nsig,
                 uint4 const * __restrict__ btabf,        /* [16][0..32768]([2^(16u)]B) */
                 u32 *         __restrict__ Pbuf,         /* P of a fixed-base signature, at its place */
                 u32 const *   __restrict__ full,         /* [slot] 0: tables j = 0 (mod 4) only, else all 32 */
-                u32 *         __restrict__ ffcnt ) {     /* the signatures that walked without doublings (FD_KC_FFS) */
+                u32 *         __restrict__ ffcnt,        /* the signatures that walked without doublings (FD_KC_FFS) */
+                uint4 const * __restrict__ wtab,         /* the wide tables of the slots below wcap */
+                u32                        wcap ) {
   size_t n = nsig;
   if( blockIdx.x < nslowblk ) {
     /* the first blocks take the head of the slow list (full 253-bit walk,
@@ -1558,10 +1660,18 @@ fd_dsmh_kernel( u32                      nsig,
       u32 fi = walk ? fidx[ arep[s] ] : 0u;
       unsigned long long wm = __ballot( walk );
       int allfull = __all( walk ? full[fi] != 0u : 1 );
+      /* one level more.  When every one of them is also below wcap, the wave walks 40 additions from the
+         wide tables; a wave that mixes the two kinds of full slot walks 48 from the byte tables, which both have.
+         The word FD_KC_FWS counts the former beside ffcnt[0] (FD_KC_FFS), which counts both */
+      int allwide = allfull && __all( walk ? fi < wcap : 1 );
       if( !walk ) return;
       if( allfull ) {
-        if( (int)( threadIdx.x & 63u ) == __ffsll( (long long)wm ) - 1 ) atomicAdd( ffcnt, (u32)__popcll( wm ) );
-        dsmf_full<FM>( col, n, fi, ftab, btabf, (i8 const *)digA, digB, Pbuf );
+        if( (int)( threadIdx.x & 63u ) == __ffsll( (long long)wm ) - 1 ) {
+          atomicAdd( ffcnt, (u32)__popcll( wm ) );
+          if( allwide ) atomicAdd( ffcnt + ( FD_KC_FWS - FD_KC_FFS ), (u32)__popcll( wm ) );
+        }
+        if( allwide ) dsmf_wide<FM>( col, n, fi, wtab, btabf, (i8 const *)digA, digB, Pbuf );
+        else dsmf_full<FM>( col, n, fi, ftab, btabf, (i8 const *)digA, digB, Pbuf );
       }
       else dsmf_one<FM>( col, n, fi, ftab, btabf, (i8 const *)digA, digB, Pbuf );
       return;
@@ -2650,7 +2760,7 @@ fd_keydedup_kernel( unsigned char const *    __restrict__ payload,
     u32 * c = ucnt + 3;                                       /* (FD_KC_*: the three of the split, two of the fixed-base keys, */
     for( int k=0; k<5; k++ ) c[k] = 0u;                       /*  three of the key cache; the hand brought back below the slots */
     for( int k=FD_KC_HIT; k<=FD_KC_BUILD; k++ ) c[k] = 0u;    /*  so that a batch's draws never wrap, and its start noted; */
-    for( int k=FD_KC_PTIX; k<=FD_KC_PINS; k++ ) c[k] = 0u;    /*  three of the full slots, two of the pinned keys) */
+    for( int k=FD_KC_PTIX; k<=FD_KC_FWS; k++ ) c[k] = 0u;     /*  three of the full slots, two of the pinned keys, two of the wide) */
     if( iblk ) { u32 h = c[FD_KC_HAND] % kc.fcap; c[FD_KC_HAND] = h; c[FD_KC_HAND0] = h; }
   }
   int bypass = ucnt[1] != 0u;          /* (uniform: the decode kernel of the batch before wrote it) */
@@ -2857,7 +2967,19 @@ __global__ void __launch_bounds__( FD_WG )
 fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 * __restrict__ fidx,
                     u32 * __restrict__ flist, unsigned char const * __restrict__ payload,
                     fdgpu_txn_desc_t const * __restrict__ desc, u32 const * __restrict__ map, fd_kcache kc,
-                    u32 cblk, uint4 * __restrict__ fbase ) {
+                    u32 cblk, uint4 * __restrict__ fbase,
+                    /* the blocks from cblk + pblk on: the 16 extra base points of the promoted slots below
+                       wcap, one lane per (slot, t, r): 11 r doublings from the slot's P_4t */
+                    u32 pblk, uint4 * __restrict__ wbase, u32 wcap ) {
+  if( blockIdx.x >= cblk + pblk ) {
+    u32 i = ( blockIdx.x - cblk - pblk ) * FD_WG + threadIdx.x;
+    u32 np = cnt[FD_KC_PTIX]; np = np < kc.pmax ? np : kc.pmax;
+    if( ( i >> 4 ) >= np ) return;
+    u32 slot = kc.plist[ i >> 4 ];
+    if( slot >= wcap ) return;
+    wbase_chain( wbase, fbase, slot, i & 15u );
+    return;
+  }
   if( blockIdx.x >= cblk ) {
     /* the blocks after the claims' (DESIGN 18): the promoted slots' P_j for j = 4t + r, r = 1..3, one lane per
        (slot, j).  The key's A is not decoded in this batch, so the chain of 8r doublings starts from the slot's own
@@ -2868,12 +2990,8 @@ fd_keyclaim_kernel( u32 const * __restrict__ mlist, u32 * __restrict__ cnt, u32 
     u32 p = i / 24u, q = i % 24u;
     if( p >= np ) return;
     u32 slot = kc.plist[p], t = q / 3u, r = q % 3u + 1u;
-    uint4 const * e = fbase + ( (size_t)slot * FD_FB_NT + 4u*t ) * 8;
-    fe ypx, ymx; ge_p3 A;
-    fe_from_quads( ypx, e[0], e[1] ); fe_from_quads( ymx, e[2], e[3] ); fe_from_quads( A.Z, e[4], e[5] );
-    fe_sub( A.X, ypx, ymx ); fe_wcarry( A.X, A.X );
-    fe_add( A.Y, ypx, ymx ); fe_wcarry( A.Y, A.Y );
-    fe_add( A.Z, A.Z, A.Z ); fe_wcarry( A.Z, A.Z ); A.T = fe_zero();
+    ge_p3 A;
+    cached_to_dbl_input( A, fbase + ( (size_t)slot * FD_FB_NT + 4u*t ) * 8 );
     fbase_chain( fbase, slot, 4u*t + r, A, 8*(int)r );
     return;
   }
@@ -2931,6 +3049,21 @@ fd_keypin_kernel( u32 m, u32 const * __restrict__ key, unsigned char * __restric
   fe_neg( A.X, A.X ); fe_wcarry( A.X, A.X );              /* -A */
   fe_mul( A.T, A.X, A.Y );
   fbase_chain( fbase, slot, j, A, 8*(int)j );
+}
+
+/* Wide tables of slots that are filled at once: the 16 extra base points of the slots flist[] names, 16
+   lanes a slot, after their P_4t are stored -- behind fd_keypin_kernel at pin time, and behind the hash launch's
+   fbase_build blocks when a claim fills its slot (fdgpu_debug_opts_t.key_full = 2).  cnt: the FD_KC_* words that hold
+   the count of flist[]; stat[ flist[2k+1] ] the key's status.  A promoted slot's are built in fd_keyclaim_kernel's
+   launch instead. */
+__global__ void __launch_bounds__( FD_WG )
+fd_wbase_kernel( u32 const * __restrict__ cnt, u32 const * __restrict__ flist, unsigned char const * __restrict__ stat,
+                 uint4 const * __restrict__ fbase, uint4 * __restrict__ wbase, u32 wcap ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( ( i >> 4 ) >= cnt[FD_KC_BUILD] ) return;
+  u32 slot = flist[ 2u*( i >> 4 ) ];
+  if( slot >= wcap || ( stat[ flist[ 2u*( i >> 4 ) + 1u ] ] & 7u ) ) return;
+  wbase_chain( wbase, fbase, slot, i & 15u );
 }
 
 /* the HA dedup seeds of a batch (kernel argument): seed[0], or with nseed > 0 seed[ the record's seed index ]
@@ -3314,6 +3447,10 @@ struct fdgpu_ed25519_ctx {
   u32 *   d_orderh;              /*   [max_sig] the hot signatures as the split lists them (ks_sig) */
   uint4 * d_fbase;               /*   [fb_cap][32][8] [2^(8j)](-A), cached form */
   uint4 * d_ftab;                /*   [fb_cap][32][128][6] the keys' tables, 384 KB per slot: 1.5 GiB at FD_FB_CAP */
+  u32     wcap;                  /*   wide tables: slots [0, wcap) have them once full; min( fb_cap, FD_FB_WCAP ), 0 with
+                                      fdgpu_debug_opts_t.key_wide = 1, fb_cap / 2 with key_wide = 2 */
+  uint4 * d_wbase;               /*   [wcap][8][2][8] [2^(32t + 11r)](-A), r = 1, 2, cached form */
+  uint4 * d_wtab;                /*   [6] the identity entry, then [wcap][8][FD_FB_WE][6]: 1.97 MB per slot, 1.9 GiB at FD_FB_WCAP */
   uint4 * d_btabf;               /*   [16][FD_BTAB_ENTRIES][6] [0..32768]([2^(16u)]B), 50 MB */
   u32 *   d_fslow;               /*   [max_sig] the fixed-base places whose R needs its decode (fd_rslow_kernel) */
   hipEvent_t ev[5];
@@ -3530,7 +3667,8 @@ enum {
   FD_SW_FBSLOW   = 9,   /* the count of the fixed-base R check's list (d_fslow) */
   FD_SW_KCACHE   = 10,  /* the key cache's hits, misses and builds, the hand's start and the hand (FD_KC_HIT.., counted from
                            FD_SW_HOT); the hand alone outlives a batch */
-  FD_SW_CNT      = 20 };                /* (... and the full slots' tickets, keys and signatures, DESIGN 18: FD_KC_PTIX..) */
+  FD_SW_CNT      = 24 };                /* (... and the full slots' tickets, keys and signatures, DESIGN 18: FD_KC_PTIX..,
+                                           the pinned keys' and the wide tables' counts, DESIGN 19, 20: ..FD_KC_FWS) */
 static u32 * slow_word( fdgpu_ed25519_ctx_t const * ctx, int w ) { return ctx->d_slow + ctx->max_sig + w; }
 
 /* What every kernel launch of one batch shares */
@@ -3582,7 +3720,7 @@ static int launch_latency( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b, int la
                         ctx->d_pstat, ctx->d_htop, 1, ctx->semantics, (u32 const *)NULL, (u32 const *)NULL,
                         (u32 const *)NULL, (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL,
                         (u32 const *)NULL, (uint4 const *)NULL, (uint4 const *)NULL, (u32 *)NULL, (u32 const *)NULL,
-                        (u32 *)NULL );
+                        (u32 *)NULL, (uint4 const *)NULL, 0u );
   else                                         /* one lane, full length (no carry fold up to nofold_max) */
     hipLaunchKernelGGL( ( nsig <= ctx->nofold_max ? fd_dsm_kernel<0> : fd_dsm_kernel<1> ), dim3(sg), dim3(FD_WG), 0, st,
                         nsig, ctx->d_tab, ctx->d_Rxy, ctx->d_digA, ctx->d_digB, ctx->d_btab, code, ctx->d_P, 0 );
@@ -3653,9 +3791,11 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
         /* (... and, in the blocks after, the P_j of the slots fd_keyclass_kernel promoted: 24 lanes a slot, the
            worst case of pmax slots, blocks beyond the device-side count return at once) */
         unsigned cblk = (unsigned)( ( fkeys + FD_WG - 1UL ) / FD_WG ), pbk = (unsigned)( ( 24UL * ctx->pmax + FD_WG - 1 ) / FD_WG );
-        hipLaunchKernelGGL( fd_keyclaim_kernel, dim3( cblk + pbk ), dim3(FD_WG), 0, st,
+        /* (... and behind those the 16 extra base points of the promoted slots below wcap) */
+        unsigned wbk = ctx->wcap ? (unsigned)( ( 16UL * ctx->pmax + FD_WG - 1 ) / FD_WG ) : 0u;
+        hipLaunchKernelGGL( fd_keyclaim_kernel, dim3( cblk + pbk + wbk ), dim3(FD_WG), 0, st,
                             (u32 const *)ctx->d_mlist, slow_word( ctx, FD_SW_HOT ), ctx->d_fidx, ctx->d_flist, b.d_payload,
-                            b.d_desc, (u32 const *)ctx->d_map, kc, (u32)cblk, ctx->d_fbase );
+                            b.d_desc, (u32 const *)ctx->d_map, kc, (u32)cblk, ctx->d_fbase, (u32)pbk, ctx->d_wbase, ctx->wcap );
       }
     }
     if( ks )
@@ -3673,7 +3813,8 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       kd ? ctx->d_astat : (unsigned char *)NULL, kd ? (u32)sg : 0u, kf ? order : (u32 const *)NULL,
                       (u32 const *)( kf ? ctx->d_orderh : NULL ), kf ? kscnt : (u32 const *)NULL,
                       (u32 const *)( kf ? ctx->d_kcnt : NULL ), kf ? fbm : 0u, (u32 const *)( kf ? ctx->d_fidx : NULL ),
-                      (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch, (u32 const *)( kf ? ctx->d_sfull : NULL ) );
+                      (u32 const *)( kf ? ctx->d_sbirth : NULL ), kc.batch, (u32 const *)( kf ? ctx->d_sfull : NULL ),
+                      kf ? ctx->wcap : 0u );
   if( ctx->timing ) hipEventRecord( b.ev[4], st );     /* (the decode kernel's own time, fdgpu_ed25519_kernel_ms 3) */
   /* ks: the high tables of the hot keys in the first hb blocks (two lanes per key, the worst case of nsig / hot_min
      keys; blocks beyond the device-side count return at once), then the hot and the cold blocks */
@@ -3695,10 +3836,21 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       ks ? ctx->d_htab : (uint4 *)NULL, (u32)hb, (u32 const *)( kf ? ctx->d_orderh : NULL ),
                       (u32 const *)( kf ? ctx->d_flist : NULL ), kf ? ctx->d_fbase : (uint4 *)NULL, (u32)fbk,
                       kf ? ctx->d_sstat : (unsigned char *)NULL, kf ? ctx->d_Rxy : (uint4 *)NULL, (u32)lpk );
-  if( fkeys )
-    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( cg * fkeys + 3UL * pkeys + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt,
+  if( fkeys ) {
+    /* the wide tables of the slots below wcap, 24 items a slot: of the promoted slots, and of the claims'
+       when a claim fills its slot at once (their 16 extra base points first, from the P_4t the hash launch stored).
+       The grid holds the worst case of both lists; wcap = 0: the parent's launches */
+    unsigned wnow = ctx->wcap && ctx->kfull_mode == 2;
+    unsigned long witems = ctx->wcap ? 24UL * ( ( wnow ? fkeys : 0UL ) + pkeys ) : 0UL;
+    if( wnow )
+      hipLaunchKernelGGL( fd_wbase_kernel, dim3( (unsigned)( ( 16UL * fkeys + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st, kscnt,
+                          (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_astat, (uint4 const *)ctx->d_fbase,
+                          ctx->d_wbase, ctx->wcap );
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( cg * fkeys + 3UL * pkeys + witems + 1UL ) / 2UL ) ), dim3(FD_WG), 0, st, kscnt,
                         (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_astat, (uint4 const *)ctx->d_fbase,
-                        ctx->d_ftab, (u32)cg, (u32 const *)ctx->d_plist, ctx->pmax );
+                        ctx->d_ftab, (u32)cg, (u32 const *)ctx->d_plist, ctx->pmax, (uint4 const *)ctx->d_wbase, ctx->d_wtab,
+                        ctx->wcap, (u32)wnow );
+  }
   if( ctx->timing ) hipEventRecord( b.ev[1], st );
   /* slow list: its head in fd_dsmh_kernel's first nsb blocks (room for 1/64 of the batch), the rest (if any) in
      fd_dsm_slow_kernel */
@@ -3712,7 +3864,8 @@ static int launch_half( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
                       (uint4 const *)( ks ? ctx->d_htab : NULL ), (uint4 const *)( ks ? ctx->d_btabh : NULL ),
                       (u32 const *)( kf ? ctx->d_fidx : NULL ), (uint4 const *)( kf ? ctx->d_ftab : NULL ),
                       (uint4 const *)( kf ? ctx->d_btabf : NULL ), kf ? ctx->d_P : (u32 *)NULL,
-                      (u32 const *)( kf ? ctx->d_sfull : NULL ), kf ? slow_word( ctx, FD_SW_HOT ) + FD_KC_FFS : (u32 *)NULL );
+                      (u32 const *)( kf ? ctx->d_sfull : NULL ), kf ? slow_word( ctx, FD_SW_HOT ) + FD_KC_FFS : (u32 *)NULL,
+                      (uint4 const *)( kf ? ctx->d_wtab : NULL ), kf ? ctx->wcap : 0u );
   if( ctx->timing ) hipEventRecord( b.ev[2], st );
   if( fkeys || npin ) {
     /* the fixed-base signatures' R, compared undecoded: the full-length path's chain over the fixed-base segment of
@@ -3742,7 +3895,7 @@ static int launch_full( fdgpu_ed25519_ctx_t * ctx, fd_batch const & b ) {
   hipLaunchKernelGGL( fd_decode_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig, 0,
                       ctx->d_pstat, ctx->d_Rxy, ctx->d_Axy, (uint4 *)NULL, (uint4 *)NULL, (u32 const *)NULL,
                       (u32 *)NULL, (unsigned char *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, (u32 const *)NULL,
-                      (u32 const *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, 0u, (u32 const *)NULL );
+                      (u32 const *)NULL, 0u, (u32 const *)NULL, (u32 const *)NULL, 0u, (u32 const *)NULL, 0u );
   hipLaunchKernelGGL( fd_hash_kernel, dim3(sg), dim3(FD_WG), 0, st, b.d_payload, b.d_desc, ctx->d_map, nsig,
                       ctx->semantics, 1, ctx->d_pstat, code, ctx->d_digA, ctx->d_digB, ctx->d_Rxy,
                       (uint4 const *)ctx->d_khash );
@@ -3793,7 +3946,7 @@ static int launch_batch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_payl
 /* Test / A/B options of contexts created from now on (fdgpu_debug_set_opts).
    Process-wide, behind a mutex; the defaults are the product's choices. */
 static std::mutex g_dbg_mu;
-static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+static fdgpu_debug_opts_t g_dbg = { -1, 0u, -1L, 0, -1L, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 static void debug_opts_get( fdgpu_debug_opts_t * o ) { std::lock_guard<std::mutex> lk( g_dbg_mu ); *o = g_dbg; }
 
 extern "C" void
@@ -3897,6 +4050,9 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
         /* full slots: a batch promotes at most a quarter of the slots, which bounds its one-off cost */
         ctx->kfull_mode = dbg.key_full;
         ctx->pmax = ctx->kfull_mode == 1 ? 0u : ctx->fb_cap / 4u > 1u ? ctx->fb_cap / 4u : 1u;
+        /* wide tables: the first wcap slots get them with their byte tables of groups 1..3 */
+        ctx->wcap = dbg.key_wide == 1 ? 0u : dbg.key_wide == 2 ? ctx->fb_cap / 2u
+                  : ctx->fb_cap < (u32)FD_FB_WCAP ? ctx->fb_cap : (u32)FD_FB_WCAP;
       }
       HIPCHK( ctx_dev_alloc( ctx, &ctx->d_kidx, ( (size_t)ctx->kc_iwords + slots ) * sizeof(u32) ), -1 );   /* (cleared per batch, */
       ctx->d_ktab = ctx->d_kidx + ctx->kc_iwords;                                                        /*  launch_half) */
@@ -3932,6 +4088,11 @@ ctx_init( fdgpu_ed25519_ctx_t * ctx, int device, unsigned long max_txn, unsigned
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_orderh, ns * sizeof(u32) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fbase, fcn * FD_FB_NT * 8 * sizeof(uint4) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_ftab, fcn * FD_FB_NT * FD_FB_E * 6 * sizeof(uint4) ), -1 );
+          if( ctx->wcap ) {
+            HIPCHK( ctx_dev_alloc( ctx, &ctx->d_wbase, (size_t)ctx->wcap * 16 * 8 * sizeof(uint4) ), -1 );
+            HIPCHK( ctx_dev_alloc( ctx, &ctx->d_wtab, ( (size_t)ctx->wcap * 8 * FD_FB_WE + 1 ) * 6 * sizeof(uint4) ), -1 );
+            HIPCHK( hipMemcpyAsync( ctx->d_wtab, fd_ptab_ident_host, sizeof(fd_ptab_ident_host), hipMemcpyHostToDevice, ctx->stream ), -1 );
+          }
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_btabf, (size_t)FD_FB_NB * FD_BTAB_ENTRIES * 6 * sizeof(uint4) ), -1 );
           HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fslow, ns * sizeof(u32) ), -1 );
         }
@@ -5491,6 +5652,19 @@ fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsi
 }
 
 extern "C" int
+fdgpu_ed25519_fwide_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs ) {
+  if( keys ) *keys = 0UL;
+  if( sigs ) *sigs = 0UL;
+  if( !ctx || !ctx->half || !ctx->key_fixed || ctx->last_path != FDGPU_PATH_THROUGHPUT ) return 0;
+  if( hipSetDevice( ctx->device ) != hipSuccess || hipStreamSynchronize( ctx->stream ) != hipSuccess ) return -1;
+  u32 cnt[ 2 ] = { 0u, 0u };
+  if( hipMemcpy( cnt, slow_word( ctx, FD_SW_HOT ) + FD_KC_FWK, sizeof(cnt), hipMemcpyDeviceToHost ) != hipSuccess ) return -1;
+  if( keys ) *keys = (unsigned long)cnt[0];
+  if( sigs ) *sigs = (unsigned long)cnt[1];
+  return 0;
+}
+
+extern "C" int
 fdgpu_ed25519_pinned_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs ) {
   if( keys ) *keys = 0UL;
   if( sigs ) *sigs = 0UL;
@@ -5536,9 +5710,15 @@ fdgpu_ed25519_set_pinned_keys( fdgpu_ed25519_ctx_t * ctx, unsigned char const * 
     HIPCHK( hipMemcpy( ctx->d_skey, uniq.data(), 32UL*m, hipMemcpyHostToDevice ), -3 );
     hipLaunchKernelGGL( fd_keypin_kernel, dim3( (unsigned)( ( (unsigned long)FD_FB_NT * m + FD_WG - 1UL ) / FD_WG ) ), dim3(FD_WG), 0, s,
                         (u32)m, (u32 const *)ctx->d_skey, ctx->d_sstat, ctx->d_fbase, ctx->d_flist, pcnt );
-    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( 4UL * m + 1UL ) / 2UL ) ), dim3(FD_WG), 0, s, (u32 const *)pcnt,
-                        (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_sstat, (uint4 const *)ctx->d_fbase,
-                        ctx->d_ftab, 4u, (u32 const *)ctx->d_plist, 0u );
+    /* (... and the wide tables of the pinned slots below wcap, their 16 extra base points first) */
+    if( ctx->wcap )
+      hipLaunchKernelGGL( fd_wbase_kernel, dim3( (unsigned)( ( 16UL * m + FD_WG - 1UL ) / FD_WG ) ), dim3(FD_WG), 0, s, (u32 const *)pcnt,
+                          (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_sstat, (uint4 const *)ctx->d_fbase,
+                          ctx->d_wbase, ctx->wcap );
+    hipLaunchKernelGGL( fd_ftab_kernel, dim3( (unsigned)( ( ( ctx->wcap ? 28UL : 4UL ) * m + 1UL ) / 2UL ) ), dim3(FD_WG), 0, s,
+                        (u32 const *)pcnt, (u32 const *)ctx->d_flist, (unsigned char const *)ctx->d_sstat,
+                        (uint4 const *)ctx->d_fbase, ctx->d_ftab, 4u, (u32 const *)ctx->d_plist, 0u,
+                        (uint4 const *)ctx->d_wbase, ctx->d_wtab, ctx->wcap, 1u );
     HIPCHK( hipGetLastError(), -3 );
     HIPCHK( hipStreamSynchronize( s ), -3 );
     HIPCHK( hipMemcpy( st.data(), ctx->d_sstat, m, hipMemcpyDeviceToHost ), -3 );

@@ -413,3 +413,37 @@ FD_LAT_FN int fd_fb_old_table( int i ) { return i < 8 ? 4*i : 2*( i - 8 ); }
 FD_LAT_FN int fd_fb_full_is_base( int i ) { return ( i % 3 ) == 2; }
 FD_LAT_FN int fd_fb_full_digit( int i ) { return ( i % 3 ) == 2 ? i / 3 : 2*( i / 3 ) + ( i % 3 ); }
 FD_LAT_FN int fd_fb_full_table( int i ) { return fd_fb_full_digit( i ); }
+
+/* Wide tables.  A slot below the context's wcap that is full also has, per 32-bit span t of k, three
+   tables over wider digits: the span's value v_t = sum_{r<4} a_(4t+r) 2^(8r) of the four byte digits above is split as
+   v_t = d0 + 2^11 d1 + 2^22 d2 with d0, d1 in [-1024, 1024) and d2 what is left; a_j in [-128, 128) bounds v_t by
+   -128 (2^32 - 1) / 255 and 127 (2^32 - 1) / 255, which gives d2 in [-514, 510] (tests/test_fb_wide_schedule.py finds
+   both ends).  Wide table (t, r) = { [e]([2^(32t + 11r)](-A)) : e = 1..fd_fb_wide_entries( r ) }: FD_FB_WE entries a
+   span, 8 FD_FB_WE = 20,544 a key.  The split works on partial sums that stay far inside 32 bits (v_t itself can
+   be below -2^31).
+
+   The wide walk makes FD_FB_WIDE_ADDS = 40 additions, five per span: number i is digit i % 5 of span i / 5 from wide
+   table 3 (i / 5) + i % 5 while i % 5 < 3, else digit b_(2 (i / 5) + i % 5 - 3) of S from the base point's table of
+   the same number.  A wave that holds a full slot without wide tables makes dsmf_full's 48 additions from the byte
+   tables, which every full slot has, in all its lanes. */
+#define FD_FB_WIDE_ADDS 40
+#define FD_FB_W0        1024                       /* entries of a span's tables r = 0, 1 */
+#define FD_FB_W2        520                        /* ... and r = 2: |d2| <= 514, rounded up to a multiple of 8 */
+#define FD_FB_WE        ( 2*FD_FB_W0 + FD_FB_W2 )  /* entries of a span */
+#define FD_FB_WCAP      1024                       /* the first min( fb_cap, FD_FB_WCAP ) slots of a context have wide tables */
+FD_LAT_FN int fd_fb_wide_split( int a0, int a1, int a2, int a3, int r ) {
+  int w  = a0 + 256*a1;
+  int d0 = ( ( w + 1024 ) & 2047 ) - 1024;
+  int v1 = ( ( w - d0 ) >> 11 ) + 32*a2 + 8192*a3;   /* (v_t - d0) / 2^11, exact */
+  int d1 = ( ( v1 + 1024 ) & 2047 ) - 1024;
+  int d2 = ( v1 - d1 ) >> 11;
+  return r==0 ? d0 : r==1 ? d1 : d2;
+}
+FD_LAT_FN int fd_fb_wide_entries( int r ) { return r < 2 ? FD_FB_W0 : FD_FB_W2; }
+FD_LAT_FN int fd_fb_wide_off( int t, int r ) { return t*FD_FB_WE + r*FD_FB_W0; }   /* first entry of table (t, r) in the key's row */
+FD_LAT_FN int fd_fb_wide_is_base( int i ) { return ( i % 5 ) >= 3; }
+FD_LAT_FN int fd_fb_wide_span( int i ) { return i / 5; }
+FD_LAT_FN int fd_fb_wide_digit( int i ) { return ( i % 5 ) >= 3 ? 2*( i / 5 ) + ( i % 5 ) - 3 : i % 5; }
+FD_LAT_FN int fd_fb_wide_table( int i ) { return ( i % 5 ) >= 3 ? 2*( i / 5 ) + ( i % 5 ) - 3 : 3*( i / 5 ) + ( i % 5 ); }
+/* the additions of a wave's fixed-base walk: every walking lane wide, or every one full */
+FD_LAT_FN int fd_fb_wave_adds( int all_wide ) { return all_wide ? FD_FB_WIDE_ADDS : FD_FB_FULL_ADDS; }

@@ -49,3 +49,28 @@ fd_fb_entry_host( int d ) { return fd_fb_entry( d ); }
 
 int
 fd_fb_tables_host( int * nt, int * nb ) { *nt = FD_FB_NT; *nb = FD_FB_NB; return 0; }
+
+/* the wide walk's schedule and split (tests/test_fb_wide_schedule.py): per addition (is_base, span, digit, table);
+   a wave's additions; a span's digit; the geometry (W0, W2, entries per span, wcap) and a table's size and offset */
+int
+fd_fb_wide_sched_host( int * out ) {
+  for( int i=0; i<FD_FB_WIDE_ADDS; i++ ) {
+    out[4*i] = fd_fb_wide_is_base( i ); out[4*i+1] = fd_fb_wide_span( i ); out[4*i+2] = fd_fb_wide_digit( i ); out[4*i+3] = fd_fb_wide_table( i );
+  }
+  return FD_FB_WIDE_ADDS;
+}
+
+int
+fd_fb_wave_adds_host( int all_wide ) { return fd_fb_wave_adds( all_wide ); }
+
+int
+fd_fb_wide_split_host( int a0, int a1, int a2, int a3, int r ) { return fd_fb_wide_split( a0, a1, a2, a3, r ); }
+
+int
+fd_fb_wide_geom_host( int * w0, int * w2, int * we, int * wcap ) { *w0 = FD_FB_W0; *w2 = FD_FB_W2; *we = FD_FB_WE; *wcap = FD_FB_WCAP; return 0; }
+
+int
+fd_fb_wide_entries_host( int r ) { return fd_fb_wide_entries( r ); }
+
+int
+fd_fb_wide_off_host( int t, int r ) { return fd_fb_wide_off( t, r ); }

@@ -51,7 +51,7 @@ EXPORTS = ("fd_ed25519_verify", "fd_ed25519_verify_batch_single_msg", "fd_ed2551
            "fdgpu_ed25519_reserve_gather_cus", "fdgpu_ed25519_reserve_cus", "fdgpu_ed25519_set_cu_exclusive", "fdgpu_ed25519_get_cu_exclusive", "fdgpu_ed25519_set_lat_share", "fdgpu_ed25519_gather_stats", "fdgpu_ed25519_phase_stats", "fdgpu_ed25519_prepare", "fdgpu_ed25519_submit_raw_gather_dev", "fdgpu_host_region",
            "fdgpu_ed25519_dropin_init", "fdgpu_debug_set_opts", "fdgpu_debug_gather_pauses",
            "fdgpu_ed25519_pipeline_state", "fdgpu_ed25519_verify_many_host", "fdgpu_sha512_batch_device", "fdgpu_sha512_batch_host", "fdgpu_ed25519_set_timing", "fdgpu_ed25519_set_small_batch_max", "fdgpu_ed25519_kernel_ms", "fdgpu_mad_peak_per_s",
-           "fdgpu_ed25519_faulted", "fdgpu_ed25519_debug_fault", "fdgpu_ed25519_slow_count", "fdgpu_ed25519_key_count", "fdgpu_ed25519_hot_count", "fdgpu_ed25519_fixed_count", "fdgpu_ed25519_fcache_count", "fdgpu_ed25519_ffull_count", "fdgpu_ed25519_set_pinned_keys", "fdgpu_ed25519_pin_cap", "fdgpu_ed25519_pinned_count", "fdgpu_ed25519_set_dedup",
+           "fdgpu_ed25519_faulted", "fdgpu_ed25519_debug_fault", "fdgpu_ed25519_slow_count", "fdgpu_ed25519_key_count", "fdgpu_ed25519_hot_count", "fdgpu_ed25519_fixed_count", "fdgpu_ed25519_fcache_count", "fdgpu_ed25519_ffull_count", "fdgpu_ed25519_fwide_count", "fdgpu_ed25519_set_pinned_keys", "fdgpu_ed25519_pin_cap", "fdgpu_ed25519_pinned_count", "fdgpu_ed25519_set_dedup",
            "fdgpu_ed25519_set_record_fp_off", "fdgpu_ed25519_batch_stats", "fdgpu_ed25519_launch_stats", "fdgpu_ed25519_front_remaining", "fdgpu_ed25519_front_batch", "fdgpu_ed25519_verify_txn_ptrs",
            "fdgpu_ed25519_submit_raw_gather_dev_f", "fdgpu_launcher_new", "fdgpu_launcher_delete", "fdgpu_launcher_stats", "fdgpu_ed25519_set_launcher",
            "fdgpu_ed25519_submit_raw_gather_to", "fdgpu_ed25519_set_dedup_seeds", "fdgpu_ed25519_debug_fail_launch",
@@ -160,6 +160,8 @@ def load_library():
         L.fdgpu_ed25519_fcache_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_ed25519_ffull_count.restype = ctypes.c_int
         L.fdgpu_ed25519_ffull_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_ed25519_fwide_count.restype = ctypes.c_int
+        L.fdgpu_ed25519_fwide_count.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_ed25519_set_pinned_keys.restype = ctypes.c_int
         L.fdgpu_ed25519_set_pinned_keys.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p]
         L.fdgpu_ed25519_pin_cap.restype = ctypes.c_ulong
@@ -208,21 +210,22 @@ class DebugOpts(ctypes.Structure):
                 ("poll_prefetch", ctypes.c_int), ("gather_rpb", ctypes.c_int), ("gather_cu_spread", ctypes.c_int),
                 ("cu_exclusive", ctypes.c_int), ("quad_sha", ctypes.c_int), ("key_dedup", ctypes.c_int),
                 ("key_split", ctypes.c_int), ("key_fixed", ctypes.c_int), ("key_cache", ctypes.c_int),
-                ("key_full", ctypes.c_int)]
+                ("key_full", ctypes.c_int), ("key_wide", ctypes.c_int)]
 
 
 def debug_set_opts(half: int = -1, half_force_slow: int = 0, small_batch_max: int = -1, dsm_lanes: int = 0,
                    nofold_max: int = -1, gather_no_writeback: int = 0, poll_prefetch: int = 0,
                    gather_rpb: int = 0, gather_cu_spread: int = 0, cu_exclusive: int = 0, quad_sha: int = 0,
                    key_dedup: int = 0, key_split: int = 0, key_fixed: int = 0, key_cache: int = 0,
-                   key_full: int = 0) -> None:
+                   key_full: int = 0, key_wide: int = 0) -> None:
     """fdgpu_debug_set_opts: the engine path of every context created from now on (tests only; the
     defaults restore the product's choices).  small_batch_max >= 2**63 means "always the latency path"."""
     o = DebugOpts(half=half, half_force_slow=half_force_slow,
                   small_batch_max=min(small_batch_max, 2**63 - 1), dsm_lanes=dsm_lanes, nofold_max=nofold_max,
                   gather_no_writeback=gather_no_writeback, poll_prefetch=poll_prefetch, gather_rpb=gather_rpb,
                   gather_cu_spread=gather_cu_spread, cu_exclusive=cu_exclusive, quad_sha=quad_sha, key_dedup=key_dedup,
-                  key_split=key_split, key_fixed=key_fixed, key_cache=key_cache, key_full=key_full)
+                  key_split=key_split, key_fixed=key_fixed, key_cache=key_cache, key_full=key_full,
+                  key_wide=key_wide)
     load_library().fdgpu_debug_set_opts(ctypes.byref(o))
 
 
@@ -532,6 +535,14 @@ class Engine:
         k, s = ctypes.c_ulong(), ctypes.c_ulong()
         if self.L.fdgpu_ed25519_ffull_count(self.ctx, ctypes.byref(k), ctypes.byref(s)):
             raise RuntimeError("fdgpu_ed25519_ffull_count: " + last_error())
+        return int(k.value), int(s.value)
+
+    def fwide_count(self) -> tuple[int, int]:
+        """(keys, signatures) of the last batch: its fixed-base keys whose slot had wide tables, and the signatures
+        that walked 40 additions; ffull_count() includes both (0, 0 elsewhere)."""
+        k, s = ctypes.c_ulong(), ctypes.c_ulong()
+        if self.L.fdgpu_ed25519_fwide_count(self.ctx, ctypes.byref(k), ctypes.byref(s)):
+            raise RuntimeError("fdgpu_ed25519_fwide_count: " + last_error())
         return int(k.value), int(s.value)
 
     def set_pinned_keys(self, keys) -> np.ndarray:

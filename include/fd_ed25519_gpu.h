@@ -451,6 +451,24 @@ fdgpu_ed25519_fcache_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * hits, uns
 int
 fdgpu_ed25519_ffull_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs );
 
+/* Wide slots in the last batch launched on ctx.  The first
+   min( slots, 1024 ) slots of the key cache also have room for wide
+   tables: every 32-bit span of k split into digits of 11, 11 and 10 bits
+   with a table each, 20,544 entries, 1.97 MB a slot.  That is up to about
+   1.9 GiB more device memory per context, allocated with it: the full
+   amount from max_sig = 131,072 on (1,024 slots), and max_sig / 128 slots'
+   worth below that (a context of 16,384 signatures: 128 slots, 252 MB).
+   They are built when the slot becomes full (a promotion, or
+   fdgpu_ed25519_set_pinned_keys), beside its 32 byte tables, and a wave
+   whose lanes all have such a key adds 40 table entries instead of 48.
+   *keys = the batch's fixed-base keys whose slot had wide tables at the
+   walk, *sigs = the signatures that walked 40 additions;
+   fdgpu_ed25519_ffull_count counts them too.  Both 0 when ffull_count's
+   are, or with fdgpu_debug_opts_t.key_wide = 1.  Waits for the batch; 0
+   on success. */
+int
+fdgpu_ed25519_fwide_count( fdgpu_ed25519_ctx_t * ctx, unsigned long * keys, unsigned long * sigs );
+
 /* Pinned keys.  Whether a key is fixed-base is otherwise decided by each
    batch alone: the batch must hold FD_FB_MIN (128) signatures of it.  A
    caller that knows which keys will keep coming back a few dozen at a
@@ -873,6 +891,12 @@ typedef struct fdgpu_debug_opts {
                                         and its signatures walk no doubling (fdgpu_ed25519_ffull_count); 1 = off, no slot
                                         is ever promoted (A/B: the walk with 24 doublings for every key); 2 = TESTS, a
                                         claim fills its slot at once, so a single batch on a fresh context walks that way */
+  int           key_wide;            /* half-size throughput path with key_fixed on: 0 = default, the first
+                                        min( slots, 1024 ) slots of the key cache also get wide tables when they become
+                                        full, and a wave whose keys all have them adds 40 entries, not 48
+                                        (fdgpu_ed25519_fwide_count); 1 = off, no wide table is allocated or built (A/B:
+                                        exactly the kernels and launches without it); 2 = TESTS, the first half of the
+                                        slots, so that with key_cache = 2 a context has both kinds of full slot */
 } fdgpu_debug_opts_t;
 
 void
