@@ -15,7 +15,7 @@ ARCH = os.environ.get("FDGPU_ARCH", "gfx950")
 
 HIP_SRCS = ["fd_ed25519_gpu.hip"]
 HIP_DEPS = ["fd_gpu_f25519.h", "fd_gpu_sha512.h", "fd_gpu_curve.h", "fd_gpu_txn.h", "fd_gpu_lattice.h", "fd_pin_list.h",
-            "../../include/fd_ed25519_gpu.h"]
+            "fd_sig_desc.h", "../../include/fd_ed25519_gpu.h"]
 
 
 def _stale(out: str, deps: list[str]) -> bool:

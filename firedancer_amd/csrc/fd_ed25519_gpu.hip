@@ -3287,6 +3287,142 @@ fd_img_scatter_kernel( fdgpu_txn_raw_t const * __restrict__ raw, unsigned char c
   if( ( n & 1u ) && threadIdx.x==0u ) dst[n-1u] = img[(size_t)t*stride + n - 1u];
 }
 
+/* Per-signature descriptors (fdgpu_ed25519_verify_sigs_device / _host): the records of a batch,
+   named by byte offsets into the caller's arena, are packed as one-signer transactions sig | pub | msg into the
+   context's pack arena, in front of an unchanged launch_batch.  fd_sig_desc.h has the validity test, the packed
+   size and the placement rule, shared with the host.  Four kernels, then the batch, then fd_sig_flag_kernel:
+
+   fd_sig_size_kernel   one lane per descriptor: its size (96 for a bad one) and flag byte, and the exclusive
+                        prefix sum of the sizes inside the 256-record block; the block's total
+   fd_sig_scan_kernel   one workgroup: the exclusive prefix sum of the block totals, in place, 64 bits
+   fd_sig_place_kernel  one lane per record: off = block base + offset in the block; a record that ends past the
+                        capacity is flagged (and with it every later one, fd_sig_desc.h); the record's
+                        fdgpu_txn_desc_t
+   fd_sig_pack_kernel   one wavefront per record: the copy */
+#define FD_SIG_DESC_FN static inline __host__ __device__
+#include "fd_sig_desc.h"
+
+#define FD_SIG_RPB 4               /* records (wavefronts) per workgroup of fd_sig_pack_kernel, as fd_gather_kernel */
+
+/* inclusive prefix sum over the wave's 64 lanes */
+template< class T > __device__ __forceinline__ T fd_wave_scan( T x, u32 lane ) {
+#pragma unroll
+  for( u32 o=1u; o<64u; o<<=1 ) { T y = __shfl_up( x, o ); if( lane >= o ) x += y; }
+  return x;
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_sig_size_kernel( fdgpu_sig_desc_t const * __restrict__ desc, u32 n, unsigned long arena_sz, u32 * __restrict__ loc,
+                    unsigned char * __restrict__ flag, unsigned long * __restrict__ btot ) {
+  __shared__ u32 wsum[ FD_WG / 64 ];
+  u32 i = blockIdx.x * FD_WG + threadIdx.x, lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  u32 sz = 0u;
+  if( i < n ) {
+    fdgpu_sig_desc_t d = desc[i];
+    int bad;
+    sz = fd_sig_desc_size( d.sig_off, d.pub_off, d.msg_off, d.msg_sz, arena_sz, &bad );
+    flag[i] = (unsigned char)( bad ? FD_SIG_DESC_BAD : 0 );
+  }
+  u32 x = fd_wave_scan( sz, lane );                          /* (at most 256 x 65,536: no overflow in 32 bits) */
+  if( lane == 63u ) wsum[w] = x;
+  __syncthreads();
+  u32 base = 0u;
+  for( u32 k=0u; k<w; k++ ) base += wsum[k];
+  if( i < n ) loc[i] = base + x - sz;
+  if( threadIdx.x == FD_WG - 1u ) btot[ blockIdx.x ] = (unsigned long)( base + x );
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_sig_scan_kernel( unsigned long * __restrict__ btot, u32 nb ) {
+  __shared__ unsigned long long wsum[ FD_WG / 64 ];
+  u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  unsigned long long carry = 0ULL;
+  for( u32 lo=0u; lo<nb; lo+=FD_WG ) {                       /* (every lane takes every turn: the barriers are uniform) */
+    u32 i = lo + threadIdx.x;
+    unsigned long long v = i < nb ? (unsigned long long)btot[i] : 0ULL;
+    unsigned long long x = fd_wave_scan( v, lane );
+    if( lane == 63u ) wsum[w] = x;
+    __syncthreads();
+    unsigned long long base = carry, all = 0ULL;
+    for( u32 k=0u; k<FD_WG/64; k++ ) { if( k < w ) base += wsum[k]; all += wsum[k]; }
+    if( i < nb ) btot[i] = (unsigned long)( base + x - v );
+    carry += all;
+    __syncthreads();                                          /* wsum is written again next turn */
+  }
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_sig_place_kernel( fdgpu_sig_desc_t const * __restrict__ desc, u32 n, u32 const * __restrict__ loc,
+                     unsigned long const * __restrict__ btot, unsigned long cap, unsigned char * __restrict__ flag,
+                     fdgpu_txn_desc_t * __restrict__ tdesc ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i >= n ) return;
+  u32 f = flag[i];
+  u32 msg_sz = f ? 0u : desc[i].msg_sz;                      /* (a bad record: 96 zero bytes, an empty message) */
+  u32 sz = ( FD_SIG_DESC_HDR + msg_sz + 7u ) & ~7u;
+  unsigned long off = btot[ blockIdx.x ] + (unsigned long)loc[i];
+  int over = fd_sig_desc_over( off, sz, cap );
+  if( over ) flag[i] = (unsigned char)( f | FD_SIG_DESC_OVER );
+  fdgpu_txn_desc_t t;
+  t.payload_off   = over ? (u32)cap : (u32)off;              /* over: not copied; the 96 zero bytes behind the capacity */
+  t.sig_base      = i;
+  t.payload_sz    = (unsigned short)( over ? FD_SIG_DESC_HDR : FD_SIG_DESC_HDR + msg_sz );
+  t.message_off   = 96; t.acct_addr_off = 64; t.signature_off = 0; t.sig_cnt = 1;
+  tdesc[i] = t;
+}
+
+/* Destination dword j of a record (0-15 the signature, 16-23 the key, then the message), from source bytes of
+   any alignment: the aligned dword that holds its first byte, the next one from the lane above (which loaded it
+   as its own first, when it copies the same range) or by a load of its own, and a byte-align shift.  Every
+   load is an aligned dword that holds at least one byte of the range the descriptor names, so none leaves the
+   arena's own dwords.  Called by all 64 lanes together (act = 0: nothing loaded, 0 returned). */
+__device__ __forceinline__ u32
+fd_sig_fetch( unsigned long arena, fdgpu_sig_desc_t const & d, u32 j, u32 nd, u32 lane, int act ) {
+  unsigned long s; u32 last, need = 4u;
+  if(      j < 16u ) { s = arena + d.sig_off + 4u * j;                          last = j == 15u; }
+  else if( j < 24u ) { s = arena + d.pub_off + 4u * ( j - 16u );                last = j == 23u; }
+  else               { s = arena + d.msg_off + 4UL * (unsigned long)( j - 24u ); last = j + 1u == nd;
+                       if( last && ( d.msg_sz & 3u ) ) need = d.msg_sz & 3u; }
+  u32 sh = (u32)s & 3u;
+  u32 const * p = (u32 const *)( s & ~3UL );
+  u32 lo = act ? p[0] : 0u;
+  u32 hi = __shfl_down( lo, 1 );
+  if( act && ( last || lane == 63u ) ) hi = sh + need > 4u ? p[1] : 0u;
+  u32 v = __builtin_amdgcn_alignbyte( hi, lo, sh );
+  if( need < 4u ) v &= ( 1u << ( 8u * need ) ) - 1u;         /* the message's last bytes: the padding is zero */
+  return act ? v : 0u;
+}
+
+__global__ void __launch_bounds__( 64 * FD_SIG_RPB )
+fd_sig_pack_kernel( unsigned char const * __restrict__ arena, fdgpu_sig_desc_t const * __restrict__ desc,
+                    fdgpu_txn_desc_t const * __restrict__ tdesc, unsigned char const * __restrict__ flag, u32 n,
+                    unsigned char * __restrict__ pack ) {
+  u32 rec = blockIdx.x * FD_SIG_RPB + ( threadIdx.x >> 6 ), lane = threadIdx.x & 63u;
+  if( rec >= n ) return;                                      /* (wave-uniform, as everything up to the copy) */
+  u32 f = flag[ rec ];
+  if( f & FD_SIG_DESC_OVER ) return;
+  u32 * dst = (u32 *)( pack + tdesc[ rec ].payload_off );
+  if( f ) { if( lane < 24u ) dst[ lane ] = 0u; return; }
+  fdgpu_sig_desc_t d = desc[ rec ];
+  u32 nd = 24u + ( ( d.msg_sz + 3u ) >> 2 );                  /* dwords that hold bytes of the record */
+  u32 ns = 24u + ( ( ( d.msg_sz + 7u ) >> 3 ) << 1 );         /* dwords stored: the size, a multiple of 8 bytes */
+  /* 1 KiB a turn: four loads in flight per lane, then four stores of 256 contiguous bytes each */
+  for( u32 j0=0u; j0<ns; j0+=256u ) {
+    u32 v[ 4 ];
+#pragma unroll
+    for( u32 k=0u; k<4u; k++ ) { u32 j = j0 + 64u * k + lane; v[k] = fd_sig_fetch( (unsigned long)arena, d, j, nd, lane, j < nd ); }
+#pragma unroll
+    for( u32 k=0u; k<4u; k++ ) { u32 j = j0 + 64u * k + lane; if( j < ns ) dst[j] = v[k]; }
+  }
+}
+
+/* behind the batch's reduce: a flagged record's code */
+__global__ void __launch_bounds__( FD_WG )
+fd_sig_flag_kernel( unsigned char const * __restrict__ flag, u32 n, i8 * __restrict__ out ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i < n && flag[i] ) out[i] = (i8)FDGPU_ERR_DESC;
+}
+
 /* ==================================================================
    Host runtime: C ABI (include/fd_ed25519_gpu.h)
    ================================================================== */
@@ -3453,6 +3589,16 @@ struct fdgpu_ed25519_ctx {
   uint4 * d_wtab;                /*   [6] the identity entry, then [wcap][8][FD_FB_WE][6]: 1.97 MB per slot, 1.9 GiB at FD_FB_WCAP */
   uint4 * d_btabf;               /*   [16][FD_BTAB_ENTRIES][6] [0..32768]([2^(16u)]B), 50 MB */
   u32 *   d_fslow;               /*   [max_sig] the fixed-base places whose R needs its decode (fd_rslow_kernel) */
+  /* per-signature descriptors (fdgpu_ed25519_sigs_prepare): all device memory */
+  unsigned long       sg_cap;    /*   the prepared size: records are packed into [0, sg_cap) of d_sg_pack; 0 = unprepared */
+  unsigned char *     d_sg_pack; /*   [sg_cap + 2 FD_ARENA_SLACK] the pack arena; the bytes from sg_cap on stay zero (a record
+                                      past the capacity is the 96 zero bytes there, with the slack every arena has behind it) */
+  fdgpu_txn_desc_t *  d_sg_tdesc;/*   [max_sig] the records as one-signer transactions (fd_sig_place_kernel) */
+  fdgpu_sig_desc_t *  d_sg_desc; /*   [max_sig] the host form's uploaded descriptors */
+  u32 *               d_sg_loc;  /*   [max_sig] a record's offset inside its block of FD_WG records */
+  unsigned char *     d_sg_flag; /*   [max_sig] FD_SIG_DESC_BAD | FD_SIG_DESC_OVER */
+  i8 *                d_sg_out;  /*   [max_sig] the host form's codes */
+  unsigned long *     d_sg_btot; /*   [max_sig / FD_WG + 1] the blocks' totals, then their prefix sum */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
@@ -4455,6 +4601,145 @@ fdgpu_ed25519_verify_txn_ptrs( fdgpu_ed25519_ctx_t * ctx, unsigned char const * 
   return verify_chunks( ctx, cnt, out,
     [&]( unsigned long i ) { return desc[i]; },
     [&]( unsigned long i, unsigned char * b ) { memcpy( b, payloads[i], desc[i].payload_sz ); } );
+}
+
+/* ---- per-signature descriptors ------------------------------ */
+
+extern "C" int
+fdgpu_ed25519_sigs_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_packed_bytes ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_sigs_prepare: the context has faulted"; return -3; }
+  if( max_packed_bytes < FD_SIG_DESC_HDR || max_packed_bytes + FD_ARENA_SLACK > ( 1UL << 32 ) ) {
+    fd_err = "fdgpu_ed25519_sigs_prepare: bad size"; return -1;
+  }
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  size_t ns = ctx->max_sig;
+  if( !ctx->d_sg_btot ) {              /* (the last one allocated: all of them or none) */
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_desc, ns * sizeof(fdgpu_sig_desc_t) ), -2 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_loc, ns * sizeof(u32) ), -2 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_flag, ns ), -2 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_out, ns ), -2 );
+    HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_btot, ( ns / FD_WG + 1UL ) * sizeof(unsigned long) ), -2 );
+  }
+  if( max_packed_bytes <= ctx->sg_cap ) return 0;
+  /* a larger arena: nothing of the context may still read the old one */
+  HIPCHK( hipDeviceSynchronize(), -2 );
+  if( ctx->d_sg_pack ) {
+    for( size_t i=0; i<ctx->dev_mem.size(); i++ )
+      if( ctx->dev_mem[i] == (void *)ctx->d_sg_pack ) { ctx->dev_mem.erase( ctx->dev_mem.begin() + (long)i ); break; }
+    (void)hipFree( ctx->d_sg_pack );
+    ctx->d_sg_pack = NULL; ctx->sg_cap = 0UL;
+  }
+  size_t bytes = max_packed_bytes + 2UL * FD_ARENA_SLACK;
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_pack, bytes ), -2 );
+  HIPCHK( hipMemsetAsync( ctx->d_sg_pack, 0, bytes, ctx->stream ), -2 );
+  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
+  ctx->sg_cap = max_packed_bytes;
+  return 0;
+}
+
+/* the kernels of one batch of descriptors on st: size, scan, place, pack, the batch itself, the flags */
+static int
+sigs_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
+             fdgpu_sig_desc_t const * d_desc, unsigned long cnt, i8 * d_out, hipStream_t st ) {
+  u32 n = (u32)cnt;
+  unsigned nb = (unsigned)( ( cnt + FD_WG - 1 ) / FD_WG );
+  hipLaunchKernelGGL( fd_sig_size_kernel, dim3(nb), dim3(FD_WG), 0, st, d_desc, n, arena_sz, ctx->d_sg_loc, ctx->d_sg_flag,
+                      ctx->d_sg_btot );
+  hipLaunchKernelGGL( fd_sig_scan_kernel, dim3(1), dim3(FD_WG), 0, st, ctx->d_sg_btot, (u32)nb );
+  hipLaunchKernelGGL( fd_sig_place_kernel, dim3(nb), dim3(FD_WG), 0, st, d_desc, n, (u32 const *)ctx->d_sg_loc,
+                      (unsigned long const *)ctx->d_sg_btot, ctx->sg_cap, ctx->d_sg_flag, ctx->d_sg_tdesc );
+  hipLaunchKernelGGL( fd_sig_pack_kernel, dim3( (unsigned)( ( cnt + FD_SIG_RPB - 1 ) / FD_SIG_RPB ) ), dim3( 64 * FD_SIG_RPB ), 0, st,
+                      d_arena, d_desc, (fdgpu_txn_desc_t const *)ctx->d_sg_tdesc, (unsigned char const *)ctx->d_sg_flag, n,
+                      ctx->d_sg_pack );
+  HIPCHK( hipGetLastError(), -3 );
+  int rc = launch_batch( ctx, ctx->d_sg_pack, ctx->d_sg_tdesc, cnt, cnt, d_out, NULL, st );
+  if( rc ) return rc;
+  hipLaunchKernelGGL( fd_sig_flag_kernel, dim3(nb), dim3(FD_WG), 0, st, (unsigned char const *)ctx->d_sg_flag, n, d_out );
+  HIPCHK( hipGetLastError(), -3 );
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_verify_sigs_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
+                                  fdgpu_sig_desc_t const * d_desc, unsigned long cnt, unsigned long msg_bytes,
+                                  signed char * d_out, void * stream ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_sigs_device: the context has faulted"; return -3; }
+  if( !ctx->sg_cap ) { fd_err = "fdgpu_ed25519_verify_sigs_device: no fdgpu_ed25519_sigs_prepare"; return -3; }
+  if( cnt > ctx->max_sig || cnt > ctx->max_txn ) { fd_err = "batch larger than ctx"; return -1; }
+  if( msg_bytes > ctx->sg_cap || 104UL * cnt > ctx->sg_cap - msg_bytes ) {
+    fd_err = "fdgpu_ed25519_verify_sigs_device: 104 cnt + msg_bytes exceeds the prepared size"; return -1;
+  }
+  if( !cnt ) return 0;
+  if( !d_arena || !d_desc || !d_out ) { fd_err = "NULL argument"; return -1; }
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  return sigs_launch( ctx, d_arena, arena_sz, d_desc, cnt, (i8 *)d_out, stream ? (hipStream_t)stream : ctx->stream );
+}
+
+extern "C" int
+fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * arena, unsigned long arena_sz,
+                                fdgpu_sig_desc_t const * desc, unsigned long cnt, signed char * out ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_sigs_host: the context has faulted"; return -3; }
+  if( !cnt ) return 0;
+  if( !arena || !desc || !out ) { fd_err = "NULL argument"; return -1; }
+  int rc;
+  unsigned char const * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
+  if( d_arena ) {
+    /* in place: the GPU packs each chunk straight from the caller's region */
+    if( !ctx->sg_cap ) { fd_err = "fdgpu_ed25519_verify_sigs_host: no fdgpu_ed25519_sigs_prepare"; return -3; }
+    if( ( rc = sync_begin( ctx ) ) ) return rc;
+    hipStream_t st = ctx->stream;
+    unsigned long most = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
+    for( unsigned long done=0UL; done<cnt; ) {
+      unsigned long n = 0UL, used = 0UL;
+      while( done + n < cnt && n < most ) {
+        fdgpu_sig_desc_t const & d = desc[ done + n ];
+        int bad;
+        unsigned long sz = fd_sig_desc_size( d.sig_off, d.pub_off, d.msg_off, d.msg_sz, arena_sz, &bad );
+        if( used + sz > ctx->sg_cap ) break;
+        used += sz; n++;
+      }
+      if( !n ) { fd_err = "fdgpu_ed25519_verify_sigs_host: a record larger than the prepared size"; return -1; }
+      HIPCHK( hipMemcpyAsync( ctx->d_sg_desc, desc + done, n * sizeof(fdgpu_sig_desc_t), hipMemcpyHostToDevice, st ), -2 );
+      if( ( rc = sigs_launch( ctx, d_arena, arena_sz, ctx->d_sg_desc, n, ctx->d_sg_out, st ) ) ) return rc;
+      HIPCHK( hipMemcpyAsync( out + done, ctx->d_sg_out, n, hipMemcpyDeviceToHost, st ), -2 );
+      if( stream_wait( ctx, st, 1 ) ) return -2;
+      done += n;
+    }
+    return 0;
+  }
+  /* any other host memory: checked here, the good records packed through the staging slot as
+     fdgpu_ed25519_verify_many_host packs its triples, run by run between the bad ones */
+  if( ( rc = sync_ctx( ctx, 1 ) ) || ( rc = sync_begin( ctx ) ) ) return rc;
+  for( unsigned long i=0UL; i<cnt; i++ ) {
+    fdgpu_sig_desc_t const & d = desc[i];
+    if( !fd_sig_desc_bad( d.sig_off, d.pub_off, d.msg_off, d.msg_sz, arena_sz ) && 96UL + d.msg_sz + 8UL > ctx->max_payload ) {
+      fd_err = "message too long"; return -1;
+    }
+  }
+  for( unsigned long i=0UL; i<cnt; ) {
+    fdgpu_sig_desc_t const * r = desc + i;
+    if( fd_sig_desc_bad( r->sig_off, r->pub_off, r->msg_off, r->msg_sz, arena_sz ) ) { out[i++] = (signed char)FDGPU_ERR_DESC; continue; }
+    unsigned long m = 1UL;
+    while( i + m < cnt && !fd_sig_desc_bad( r[m].sig_off, r[m].pub_off, r[m].msg_off, r[m].msg_sz, arena_sz ) ) m++;
+    rc = verify_chunks( ctx, m, out + i,
+      [&]( unsigned long k ) {
+        fdgpu_txn_desc_t d = {};
+        d.payload_sz = (unsigned short)( 96U + r[k].msg_sz );
+        d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
+        return d;
+      },
+      [&]( unsigned long k, unsigned char * b ) {
+        memcpy( b, arena + r[k].sig_off, 64 ); memcpy( b + 64, arena + r[k].pub_off, 32 );
+        if( r[k].msg_sz ) memcpy( b + 96, arena + r[k].msg_off, r[k].msg_sz );
+      } );
+    if( rc ) return rc;
+    i += m;
+  }
+  return 0;
 }
 
 /* ---- batch SHA-512 ---------------------------------------------------- */

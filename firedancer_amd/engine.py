@@ -35,8 +35,13 @@ assert DESC_DTYPE.itemsize == 16
 RAW_DTYPE = np.dtype([("payload_off", "<u4"), ("sig_base", "<u4"), ("payload_sz", "<u2"), ("sig_lanes", "u1"),
                       ("_pad", "u1", (5,))])
 assert RAW_DTYPE.itemsize == 16
+SIG_DESC_DTYPE = np.dtype([("sig_off", "<u4"), ("pub_off", "<u4"), ("msg_off", "<u4"), ("msg_sz", "<u4")])
+assert SIG_DESC_DTYPE.itemsize == 16
 FDGPU_ERR_PARSE = -16
 FDGPU_ERR_OVERRUN = -17
+FDGPU_ERR_DESC = -18
+FDGPU_MSG_MAX = 65439
+ARENA_SLACK = 512            # readable bytes every device arena has behind its last byte
 TXN_IMG_STRIDE = 864
 
 # every symbol include/fd_ed25519_gpu.h declares
@@ -55,6 +60,7 @@ EXPORTS = ("fd_ed25519_verify", "fd_ed25519_verify_batch_single_msg", "fd_ed2551
            "fdgpu_ed25519_set_record_fp_off", "fdgpu_ed25519_batch_stats", "fdgpu_ed25519_launch_stats", "fdgpu_ed25519_front_remaining", "fdgpu_ed25519_front_batch", "fdgpu_ed25519_verify_txn_ptrs",
            "fdgpu_ed25519_submit_raw_gather_dev_f", "fdgpu_launcher_new", "fdgpu_launcher_delete", "fdgpu_launcher_stats", "fdgpu_ed25519_set_launcher",
            "fdgpu_ed25519_submit_raw_gather_to", "fdgpu_ed25519_set_dedup_seeds", "fdgpu_ed25519_debug_fail_launch",
+           "fdgpu_ed25519_sigs_prepare", "fdgpu_ed25519_verify_sigs_device", "fdgpu_ed25519_verify_sigs_host",
            "fdgpu_last_error")
 
 _lib = None
@@ -145,6 +151,14 @@ def load_library():
         L.fdgpu_ed25519_pipeline_state.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_ed25519_verify_txn_ptrs.restype = ctypes.c_int
         L.fdgpu_ed25519_verify_txn_ptrs.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_ulong, ctypes.c_void_p]
+        L.fdgpu_ed25519_sigs_prepare.restype = ctypes.c_int
+        L.fdgpu_ed25519_sigs_prepare.argtypes = [ctypes.c_void_p, ctypes.c_ulong]
+        L.fdgpu_ed25519_verify_sigs_device.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_sigs_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                      ctypes.c_ulong, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_ed25519_verify_sigs_host.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_sigs_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                    ctypes.c_ulong, ctypes.c_void_p]
         L.fdgpu_ed25519_faulted.restype = ctypes.c_int
         L.fdgpu_ed25519_faulted.argtypes = [ctypes.c_void_p]
         L.fdgpu_ed25519_debug_fault.argtypes = [ctypes.c_void_p]
@@ -423,6 +437,40 @@ class Engine:
         if rc:
             raise RuntimeError(f"fdgpu_ed25519_verify_txn_ptrs: {rc} {last_error()}")
         return out
+
+    # -- signatures in place, from per-signature descriptors -------------------
+    def sigs_prepare(self, max_packed_bytes: int) -> None:
+        """fdgpu_ed25519_sigs_prepare: the device buffers of verify_sigs_device and of verify_sigs_host over a
+        registered region; a batch of cnt records with msg_bytes of messages needs 104 * cnt + msg_bytes at most.
+        Raises on a refusal, with the C return value as the exception's second argument."""
+        rc = self.L.fdgpu_ed25519_sigs_prepare(self.ctx, max_packed_bytes)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_sigs_prepare: {rc} {last_error()}", rc)
+
+    def verify_sigs_host(self, arena: np.ndarray, desc: np.ndarray, arena_sz: int | None = None) -> np.ndarray:
+        """fd_ed25519_verify codes (FDGPU_ERR_DESC for a bad descriptor) of the triples that desc (SIG_DESC_DTYPE)
+        names inside the first arena_sz bytes of arena, a uint8 array.  Synchronous.  arena_sz defaults to the
+        array less ARENA_SLACK bytes, its slack: if all of that lies in a registered region (host_register) the
+        GPU reads the records in place.  Raises on a refusal, with the C return value as the exception's second
+        argument."""
+        if arena_sz is None:
+            arena_sz = arena.nbytes - ARENA_SLACK
+        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and 0 <= arena_sz <= arena.nbytes
+        desc = np.ascontiguousarray(desc, dtype=SIG_DESC_DTYPE)
+        out = np.zeros(max(len(desc), 1), np.int8)
+        rc = self.L.fdgpu_ed25519_verify_sigs_host(self.ctx, arena.ctypes.data, arena_sz,
+                                                   desc.ctypes.data, len(desc), out.ctypes.data)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_sigs_host: {rc} {last_error()}", rc)
+        return out[:len(desc)]
+
+    def verify_sigs_device(self, d_arena: int, arena_sz: int, d_desc: int, cnt: int, msg_bytes: int, d_out: int,
+                           stream: int | None = None) -> None:
+        """Enqueue a batch of descriptors resident in device memory (raw device pointers; d_arena has ARENA_SLACK
+        readable bytes behind arena_sz).  Raises on a refusal, with the C return value as the second argument."""
+        rc = self.L.fdgpu_ed25519_verify_sigs_device(self.ctx, d_arena, arena_sz, d_desc, cnt, msg_bytes, d_out, stream)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_sigs_device: {rc} {last_error()}", rc)
 
     # -- raw payloads: device fd_txn_parse + verify ---------------------------
     def verify_raw_host(self, payload: np.ndarray, off: np.ndarray, sz: np.ndarray, want_img: bool = False):

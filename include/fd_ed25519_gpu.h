@@ -255,6 +255,101 @@ fdgpu_ed25519_verify_many_host( fdgpu_ed25519_ctx_t *         ctx,
                                 unsigned long                 cnt,
                                 signed char *                 out );
 
+/* Signatures verified where they lie, from per-signature descriptors
+   (the callers of SURVEY.md §3 D whose signatures are not
+   shaped like a transaction: CRDS values inside a gossip packet, a prune's
+   two signable forms, pings and pongs, precompiles, repair and shreds).
+   Record i is the triple at byte offsets sig_off (64 bytes, R || S),
+   pub_off (32 bytes) and msg_off (msg_sz bytes) of one arena of arena_sz
+   bytes.  The offsets need no alignment and the ranges of one record, or
+   of different records, may overlap.
+
+   out[i] = fd_ed25519_verify( arena + msg_off, msg_sz, arena + sig_off,
+   arena + pub_off ) under the context's semantics, or FDGPU_ERR_DESC if
+   descriptor i is bad: sig_off + 64, pub_off + 32 or msg_off + msg_sz
+   exceeds arena_sz (computed in 64 bits: offsets near 2^32 do not wrap),
+   or msg_sz > FDGPU_MSG_MAX.  A bad descriptor causes no load outside
+   the arena and its slack and changes no other record's code.
+
+   The GPU packs every record as the one-signer transaction sig | pub |
+   msg into the context's pack arena (fd_sig_size_kernel, fd_sig_scan_kernel,
+   fd_sig_place_kernel, fd_sig_pack_kernel: one wavefront per record, aligned
+   dword loads and 256 contiguous bytes per store whatever the source
+   alignment) and hands them to the verify kernels of the other batch
+   calls, unchanged.  A bad record takes a place of 96 zero bytes there, so
+   record i is transaction i and signature i: the diagnostic counters
+   (fdgpu_ed25519_key_count and the calls after it) see it as one signature
+   of the all-zero public key over an empty message. */
+#define FDGPU_ERR_DESC   (-18)        /* descriptor i names bytes outside the arena, a message over FDGPU_MSG_MAX,
+                                         or (device form) a record that does not fit the prepared pack arena */
+#define FDGPU_MSG_MAX    (65439UL)    /* as fdgpu_ed25519_verify_many_host: 96 + msg_sz fits the 16-bit payload_sz */
+
+typedef struct fdgpu_sig_desc {       /* 16 bytes; byte offsets into the arena, no alignment required, ranges may overlap */
+  unsigned int sig_off;               /* 64 bytes: R || S */
+  unsigned int pub_off;               /* 32 bytes */
+  unsigned int msg_off;
+  unsigned int msg_sz;
+} fdgpu_sig_desc_t;
+
+/* fdgpu_ed25519_sigs_prepare: allocate what the two calls below need, all
+   of it device memory (no pinned host memory, so a context created with
+   max_payload_bytes = 0 can use the device form): the pack arena of
+   max_packed_bytes (+ slack; max_packed_bytes + 512 <= 2^32, the range of
+   payload_off), one fdgpu_txn_desc_t, one descriptor, one offset, one flag
+   and one code per record for max_sig records, and the scan's block
+   totals: 38 bytes per signature of max_sig beside the arena.  A record
+   packs to 96 + msg_sz rounded up to 8, so a batch of cnt records with
+   msg_bytes of messages never needs more than 104 cnt + msg_bytes.  A
+   control-plane call like fdgpu_ed25519_prepare (before the sandbox): it
+   waits for the device.  Calling it again with a larger size reallocates
+   the arena; with a smaller or equal one it changes nothing.
+   fdgpu_ed25519_ctx_delete frees.  0, -1 bad arguments, -2 the
+   allocation failed (the context is then unprepared), -3 faulted. */
+int
+fdgpu_ed25519_sigs_prepare( fdgpu_ed25519_ctx_t * ctx,
+                            unsigned long         max_packed_bytes );
+
+/* Device form.  d_arena (HBM, or the device view of a registered host
+   region, fdgpu_host_dev_ptr: the pack then reads it over PCIe, once) has
+   512 readable bytes after arena_sz, as every device arena here; d_desc
+   and d_out (cnt codes) are device memory.  Asynchronous on `stream` (NULL
+   = the ctx's own), like fdgpu_ed25519_verify_txns_device, and like it one
+   batch of the context at a time.  msg_bytes is the caller's sum of
+   msg_sz: -1 (nothing launched) if cnt > max_sig, cnt > max_txn or
+   104 cnt + msg_bytes exceeds the prepared size.  The device does not
+   trust msg_bytes: a record whose packed end would pass the prepared size
+   is not copied and gets FDGPU_ERR_DESC, and so does every record behind
+   it (fd_sig_desc.h).  -3 on a faulted or unprepared context. */
+int
+fdgpu_ed25519_verify_sigs_device( fdgpu_ed25519_ctx_t *    ctx,
+                                  unsigned char const *    d_arena,
+                                  unsigned long            arena_sz,
+                                  fdgpu_sig_desc_t const * d_desc,
+                                  unsigned long            cnt,
+                                  unsigned long            msg_bytes,
+                                  signed char *            d_out,
+                                  void *                   stream );
+
+/* Host form.  Synchronous; -1 while the async pipeline holds anything, as
+   the other synchronous calls.  If [arena, arena + arena_sz + 512) lies
+   inside one fdgpu_host_alloc / fdgpu_host_register-ed region, the
+   descriptors are uploaded in chunks (at most max_sig and max_txn records,
+   packed size at most the prepared size) and each chunk is packed by the
+   GPU straight from the region and verified: no host copy, one PCIe
+   crossing; this branch needs fdgpu_ed25519_sigs_prepare (-3 without).
+   Otherwise the descriptors are checked on the host and the good records
+   packed through the staging slot exactly as
+   fdgpu_ed25519_verify_many_host does (needs a ctx with staging, and -1
+   for a message that cannot fit it); a bad descriptor gets FDGPU_ERR_DESC
+   and takes no place.  Both branches give identical codes. */
+int
+fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t *    ctx,
+                                unsigned char const *    arena,
+                                unsigned long            arena_sz,
+                                fdgpu_sig_desc_t const * desc,
+                                unsigned long            cnt,
+                                signed char *            out );
+
 /* fdgpu_ed25519_verify_txn_ptrs: out[i] = the fd_ed25519_verify_batch_
    single_msg code of transaction i, whose payload is at payloads[i] (any
    host memory) and whose fd_txn_t fields are in desc[i] (signature_off,
