@@ -58,6 +58,7 @@
    only the table index is data dependent. */
 
 #include "fd_gpu_sha512.h"
+#include "fd_gpu_sha256.h"
 #include "fd_gpu_curve.h"
 #include "fd_gpu_txn.h"
 #include "fd_gpu_lattice.h"
@@ -3423,6 +3424,125 @@ fd_sig_flag_kernel( unsigned char const * __restrict__ flag, u32 n, i8 * __restr
   if( i < n && flag[i] ) out[i] = (i8)FDGPU_ERR_DESC;
 }
 
+/* Batch SHA-256, the sibling of fd_sha512_batch_kernel: hash + 32 t = SHA-256( data[ off[t], off[t]+sz[t] ) ) */
+__global__ void __launch_bounds__( FD_WG )
+fd_sha256_batch_kernel( unsigned char const * __restrict__ data, unsigned long const * __restrict__ off,
+                        unsigned int const * __restrict__ sz, u32 cnt, uint4 * __restrict__ hash ) {
+  u32 t = blockIdx.x * FD_WG + threadIdx.x;
+  if( t >= cnt ) return;
+  u32 h[8];
+  fd_sha256_bytes( h, data + off[t], sz[t] );
+  uint4 * o = hash + (size_t)t*2;
+#pragma unroll
+  for( int i=0; i<2; i++ ) o[i] = make_uint4( fd_bswap32( h[4*i] ), fd_bswap32( h[4*i+1] ), fd_bswap32( h[4*i+2] ), fd_bswap32( h[4*i+3] ) );
+}
+
+/* Merkle shreds (fdgpu_ed25519_verify_shreds_device / _host): the message a shred's leader signed is
+   the root of its FEC set's Merkle tree, which a verifier derives from the shred and the proof it carries.
+   fd_shred_desc.h has the rules that decide a record's code before any hashing, shared with the host.  Three
+   kernels around an unchanged launch_batch over the batch's sig_cnt signature slots:
+
+   fd_shred_slot_kernel  one lane per signature slot: 128 zero bytes at pack + 128 s and the slot's
+                         fdgpu_txn_desc_t, a one-signer transaction of 96 bytes with an empty message -- what a
+                         slot is if no good record names it (the form fd_sig_place_kernel gives a bad record)
+   fd_shred_root_kernel  one lane per record: the code of the descriptor, parse and Merkle rules; for a good
+                         record the leaf (fd_sha256_shred_leaf: 15-19 blocks read where the shred lies) and one
+                         merge per proof node (two blocks, the second made in registers), the root to root + 32 i,
+                         and, if it names a key, sig | key | root to its slot with payload_sz 128
+   fd_shred_flag_kernel  behind the batch: out[i] = the record's flagged code, else 0 without a key, else its
+                         slot's code
+
+   No load leaves the arena and its slack: a bad descriptor loads nothing; a shred under 88 bytes loads nothing; a
+   longer one loads its header fields (the dwords of [64, 92)); a parsed one has sz >= 1203 or 1228 and is read to
+   at most 67 bytes past that. */
+#define FD_SHRED_DESC_FN static inline __host__ __device__
+#include "fd_shred_desc.h"
+
+#define FD_SHRED_SLOT 128UL        /* bytes of a signature slot of the pack: sig | key | root */
+
+__global__ void __launch_bounds__( FD_WG )
+fd_shred_slot_kernel( uint4 * __restrict__ pack, fdgpu_txn_desc_t * __restrict__ tdesc, u32 nsig ) {
+  u32 s = blockIdx.x * FD_WG + threadIdx.x;
+  if( s >= nsig ) return;
+  uint4 * p = pack + (size_t)s * ( FD_SHRED_SLOT / 16UL );
+#pragma unroll
+  for( int k=0; k<8; k++ ) p[k] = make_uint4( 0u, 0u, 0u, 0u );
+  fdgpu_txn_desc_t t;
+  t.payload_off = (u32)( FD_SHRED_SLOT * s ); t.sig_base = s; t.payload_sz = 96;
+  t.message_off = 96; t.acct_addr_off = 64; t.signature_off = 0; t.sig_cnt = 1;
+  tdesc[s] = t;
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_shred_root_kernel( unsigned char const * __restrict__ arena, unsigned long arena_sz,
+                      fdgpu_shred_desc_t const * __restrict__ desc, u32 n, u32 nsig,
+                      uint4 const * __restrict__ keys, u32 nkey, uint4 * __restrict__ pack,
+                      fdgpu_txn_desc_t * __restrict__ tdesc, i8 * __restrict__ flag, uint4 * __restrict__ root ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i >= n ) return;
+  fdgpu_shred_desc_t d = desc[i];
+  unsigned char const * sh = arena + d.off;
+  fd_shred_info_t in = { 0U, 0U, 0U };
+  int code;
+  if( fd_shred_desc_bad( d.off, d.sz, d.key_idx, d.sig_idx, arena_sz, nkey, nsig ) ) code = FD_SHRED_ERR_DESC;
+  else {
+    fd_shred_fields_t f = {};
+    if( d.sz >= FD_SHRED_HDR_SZ ) {
+      u32 w[ FD_SHRED_FIELD_WORDS ];
+      fd_load_words<FD_SHRED_FIELD_WORDS>( w, sh + 64 );
+      fd_shred_fields( w, &f );
+    }
+    code = fd_shred_classify( &f, d.sz, d.flags, &in );
+  }
+  u32 h[8];
+#pragma unroll
+  for( int k=0; k<8; k++ ) h[k] = 0u;
+  if( !code ) {
+    fd_sha256_shred_leaf( h, sh + 64, in.moff - 64u );
+#pragma unroll 1
+    for( u32 l=0u; l<in.depth; l++ ) {
+      u32 s[5];
+      fd_load_words<5>( s, sh + in.moff + FD_SHRED_NODE_SZ * l );
+#pragma unroll
+      for( int k=0; k<5; k++ ) s[k] = fd_bswap32( s[k] );
+      fd_sha256_shred_merge( h, s, (int)( ( in.leaf >> l ) & 1u ) );
+    }
+#pragma unroll
+    for( int k=0; k<8; k++ ) h[k] = fd_bswap32( h[k] );     /* the root's bytes as little-endian words */
+  }
+  flag[i] = (i8)code;
+  if( root ) {                                               /* (a flagged record's root: 32 zero bytes) */
+    root[ 2UL*i     ] = make_uint4( h[0], h[1], h[2], h[3] );
+    root[ 2UL*i+1UL ] = make_uint4( h[4], h[5], h[6], h[7] );
+  }
+  if( !code && d.key_idx != FD_SHRED_NO_SIG ) {
+    u32 sg[16];
+    fd_load_words<16>( sg, sh );
+    uint4 const * k = keys + 2UL * d.key_idx;
+    uint4 k0 = k[0], k1 = k[1];
+    uint4 * p = pack + (size_t)d.sig_idx * ( FD_SHRED_SLOT / 16UL );
+#pragma unroll
+    for( int q=0; q<4; q++ ) p[q] = make_uint4( sg[4*q], sg[4*q+1], sg[4*q+2], sg[4*q+3] );
+    p[4] = k0; p[5] = k1;
+    p[6] = make_uint4( h[0], h[1], h[2], h[3] );
+    p[7] = make_uint4( h[4], h[5], h[6], h[7] );
+    fdgpu_txn_desc_t t;
+    t.payload_off = (u32)( FD_SHRED_SLOT * d.sig_idx ); t.sig_base = d.sig_idx; t.payload_sz = 128;
+    t.message_off = 96; t.acct_addr_off = 64; t.signature_off = 0; t.sig_cnt = 1;
+    tdesc[ d.sig_idx ] = t;
+  }
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_shred_flag_kernel( fdgpu_shred_desc_t const * __restrict__ desc, u32 n, i8 const * __restrict__ flag,
+                      i8 const * __restrict__ code, i8 * __restrict__ out ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i >= n ) return;
+  i8 f = flag[i];
+  if( !f && desc[i].key_idx != FD_SHRED_NO_SIG ) f = code[ desc[i].sig_idx ];   /* (not flagged: sig_idx < sig_cnt) */
+  out[i] = f;
+}
+
 /* ==================================================================
    Host runtime: C ABI (include/fd_ed25519_gpu.h)
    ================================================================== */
@@ -3599,6 +3719,18 @@ struct fdgpu_ed25519_ctx {
   unsigned char *     d_sg_flag; /*   [max_sig] FD_SIG_DESC_BAD | FD_SIG_DESC_OVER */
   i8 *                d_sg_out;  /*   [max_sig] the host form's codes */
   unsigned long *     d_sg_btot; /*   [max_sig / FD_WG + 1] the blocks' totals, then their prefix sum */
+  /* Merkle shreds (fdgpu_ed25519_shreds_prepare): all device memory */
+  unsigned long       sh_max;    /*   records a batch may hold; 0 = unprepared */
+  unsigned long       sh_keys;   /*   keys a batch may name */
+  unsigned long       sh_sig;    /*   signature slots: min( max_sig, max_txn, sh_max ) */
+  unsigned char *     d_sh_pack; /*   [128 sh_sig + 2 FD_ARENA_SLACK] the slots, sig | key | root */
+  fdgpu_txn_desc_t *  d_sh_tdesc;/*   [sh_sig] the slots as one-signer transactions */
+  i8 *                d_sh_code; /*   [sh_sig] the batch's code of each slot */
+  i8 *                d_sh_flag; /*   [sh_max] a record's flagged code, 0 = none */
+  fdgpu_shred_desc_t * d_sh_desc;/*   [sh_max] the host form's uploaded descriptors */
+  i8 *                d_sh_out;  /*   [sh_max] the host form's codes */
+  unsigned char *     d_sh_root; /*   [32 sh_max] the host form's roots */
+  unsigned char *     d_sh_keys; /*   [32 sh_keys] the host form's keys */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
@@ -4740,6 +4872,195 @@ fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
     i += m;
   }
   return 0;
+}
+
+/* ---- Merkle shreds ------------------------------------------ */
+
+#define FD_SHRED_STRIDE 1232UL     /* the host form's staging: a shred's first min( sz, 1228 ) bytes every 1,232 */
+
+template< class T > static void
+ctx_dev_free( fdgpu_ed25519_ctx_t * ctx, T ** p ) {
+  if( !*p ) return;
+  for( size_t i=0; i<ctx->dev_mem.size(); i++ )
+    if( ctx->dev_mem[i] == (void *)*p ) { ctx->dev_mem.erase( ctx->dev_mem.begin() + (long)i ); break; }
+  (void)hipFree( *p );
+  *p = NULL;
+}
+
+extern "C" int
+fdgpu_ed25519_shreds_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_shreds, unsigned long max_keys ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_shreds_prepare: the context has faulted"; return -3; }
+  if( !max_shreds || max_shreds >= ( 1UL << 31 ) || !max_keys || max_keys > (unsigned long)FD_SHRED_NO_SIG ) {
+    fd_err = "fdgpu_ed25519_shreds_prepare: bad size"; return -1;
+  }
+  if( max_shreds <= ctx->sh_max && max_keys <= ctx->sh_keys ) return 0;
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  if( max_shreds < ctx->sh_max  ) max_shreds = ctx->sh_max;
+  if( max_keys   < ctx->sh_keys ) max_keys   = ctx->sh_keys;
+  /* larger buffers: nothing of the context may still read the old ones */
+  HIPCHK( hipDeviceSynchronize(), -2 );
+  ctx->sh_max = 0UL; ctx->sh_keys = 0UL; ctx->sh_sig = 0UL;
+  ctx_dev_free( ctx, &ctx->d_sh_pack ); ctx_dev_free( ctx, &ctx->d_sh_tdesc ); ctx_dev_free( ctx, &ctx->d_sh_code );
+  ctx_dev_free( ctx, &ctx->d_sh_flag ); ctx_dev_free( ctx, &ctx->d_sh_desc );  ctx_dev_free( ctx, &ctx->d_sh_out );
+  ctx_dev_free( ctx, &ctx->d_sh_root ); ctx_dev_free( ctx, &ctx->d_sh_keys );
+  size_t ns = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
+  if( ns > max_shreds ) ns = max_shreds;
+  if( ns > ( 1UL << 24 ) ) ns = 1UL << 24;                   /* (128 ns + slack inside payload_off's 32 bits) */
+  size_t pack = FD_SHRED_SLOT * ns + 2UL * FD_ARENA_SLACK;
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_pack, pack ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_code, ns ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_flag, max_shreds ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_desc, max_shreds * sizeof(fdgpu_shred_desc_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_out, max_shreds ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_root, 32UL * max_shreds ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_keys, 32UL * max_keys ), -2 );
+  HIPCHK( hipMemsetAsync( ctx->d_sh_pack, 0, pack, ctx->stream ), -2 );
+  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
+  ctx->sh_max = max_shreds; ctx->sh_keys = max_keys; ctx->sh_sig = ns;
+  return 0;
+}
+
+/* the kernels of one batch of shreds on st: the slots, the roots, the batch over the slots, the codes */
+static int
+shreds_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
+               fdgpu_shred_desc_t const * d_desc, unsigned long cnt, unsigned long sig_cnt, unsigned char const * d_keys,
+               unsigned long key_cnt, i8 * d_out, unsigned char * d_root, hipStream_t st ) {
+  unsigned nb = (unsigned)( ( cnt + FD_WG - 1 ) / FD_WG );
+  if( sig_cnt )
+    hipLaunchKernelGGL( fd_shred_slot_kernel, dim3( (unsigned)( ( sig_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
+                        (uint4 *)ctx->d_sh_pack, ctx->d_sh_tdesc, (u32)sig_cnt );
+  hipLaunchKernelGGL( fd_shred_root_kernel, dim3(nb), dim3(FD_WG), 0, st, d_arena, arena_sz, d_desc, (u32)cnt, (u32)sig_cnt,
+                      (uint4 const *)d_keys, (u32)key_cnt, (uint4 *)ctx->d_sh_pack, ctx->d_sh_tdesc, ctx->d_sh_flag,
+                      (uint4 *)d_root );
+  HIPCHK( hipGetLastError(), -3 );
+  if( sig_cnt ) {
+    int rc = launch_batch( ctx, ctx->d_sh_pack, ctx->d_sh_tdesc, sig_cnt, sig_cnt, ctx->d_sh_code, NULL, st );
+    if( rc ) return rc;
+  } else ctx->last_path = FDGPU_PATH_NONE;                    /* a batch without signatures */
+  hipLaunchKernelGGL( fd_shred_flag_kernel, dim3(nb), dim3(FD_WG), 0, st, d_desc, (u32)cnt, (i8 const *)ctx->d_sh_flag,
+                      (i8 const *)ctx->d_sh_code, d_out );
+  HIPCHK( hipGetLastError(), -3 );
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_verify_shreds_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
+                                    fdgpu_shred_desc_t const * d_desc, unsigned long cnt, unsigned long sig_cnt,
+                                    unsigned char const * d_keys, unsigned long key_cnt, signed char * d_out,
+                                    unsigned char * d_root, void * stream ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_shreds_device: the context has faulted"; return -3; }
+  if( !ctx->sh_max ) { fd_err = "fdgpu_ed25519_verify_shreds_device: no fdgpu_ed25519_shreds_prepare"; return -3; }
+  if( cnt > ctx->sh_max || sig_cnt > ctx->sh_sig || key_cnt > ctx->sh_keys ) { fd_err = "batch larger than prepared"; return -1; }
+  if( !cnt ) return 0;
+  if( !d_arena || !d_desc || !d_out || ( key_cnt && !d_keys ) ) { fd_err = "NULL argument"; return -1; }
+  if( ( (uintptr_t)d_keys | (uintptr_t)d_root ) & 15UL ) { fd_err = "d_keys and d_root are 16-byte aligned"; return -1; }
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  return shreds_launch( ctx, d_arena, arena_sz, d_desc, cnt, sig_cnt, d_keys, key_cnt, (i8 *)d_out, d_root,
+                        stream ? (hipStream_t)stream : ctx->stream );
+}
+
+extern "C" int
+fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * arena, unsigned long arena_sz,
+                                  fdgpu_shred_desc_t const * desc, unsigned long cnt, unsigned char const * keys,
+                                  unsigned long key_cnt, signed char * out, unsigned char * root ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_shreds_host: the context has faulted"; return -3; }
+  if( !ctx->sh_max ) { fd_err = "fdgpu_ed25519_verify_shreds_host: no fdgpu_ed25519_shreds_prepare"; return -3; }
+  if( key_cnt > ctx->sh_keys ) { fd_err = "more keys than prepared"; return -1; }
+  if( !cnt ) return 0;
+  if( !arena || !desc || !out || ( key_cnt && !keys ) ) { fd_err = "NULL argument"; return -1; }
+  int rc;
+  unsigned char const * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
+  unsigned long most = ctx->sh_max;
+  if( !d_arena ) {
+    /* any other host memory: the shreds go through the staging slot, one every FD_SHRED_STRIDE bytes */
+    if( ( rc = sync_ctx( ctx, 1 ) ) ) return rc;
+    unsigned long fit = ctx->max_payload / FD_SHRED_STRIDE;
+    if( !fit ) { fd_err = "the staging slot holds no shred"; return -1; }
+    if( most > fit ) most = fit;
+  }
+  if( ( rc = sync_begin( ctx ) ) ) return rc;
+  hipStream_t st = ctx->stream;
+  fd_slot & sl = ctx->slot[0];
+  if( key_cnt ) HIPCHK( hipMemcpyAsync( ctx->d_sh_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
+  std::vector<fdgpu_shred_desc_t> tmp( most < cnt ? most : cnt );
+  for( unsigned long done=0UL; done<cnt; ) {
+    /* the chunk: records up to the prepared count, signatures -- numbered here, in order -- up to the slots */
+    unsigned long n = 0UL, nsig = 0UL;
+    while( done + n < cnt && n < most ) {
+      fdgpu_shred_desc_t d = desc[ done + n ];
+      if( d.key_idx != FD_SHRED_NO_SIG ) {
+        if( nsig == ctx->sh_sig ) break;
+        d.sig_idx = (unsigned int)nsig++;
+      }
+      if( !d_arena ) {
+        if( (unsigned long)d.off + (unsigned long)d.sz > arena_sz ) { d.off = 0xFFFFFFFFU; d.sz = 0xFFFFU; }   /* stays bad */
+        else {
+          unsigned short sz = d.sz < 1228U ? d.sz : (unsigned short)1228U;
+          memcpy( sl.h_payload + FD_SHRED_STRIDE * n, arena + d.off, sz );
+          d.off = (unsigned int)( FD_SHRED_STRIDE * n ); d.sz = sz;
+        }
+      }
+      tmp[ n++ ] = d;
+    }
+    unsigned char const * da = d_arena; unsigned long dsz = arena_sz;
+    if( !d_arena ) {
+      dsz = FD_SHRED_STRIDE * n;
+      memset( sl.h_payload + dsz, 0, FD_ARENA_SLACK );
+      HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, dsz + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
+      da = sl.d_payload;
+    }
+    HIPCHK( hipMemcpyAsync( ctx->d_sh_desc, tmp.data(), n * sizeof(fdgpu_shred_desc_t), hipMemcpyHostToDevice, st ), -2 );
+    if( ( rc = shreds_launch( ctx, da, dsz, ctx->d_sh_desc, n, nsig, ctx->d_sh_keys, key_cnt, ctx->d_sh_out,
+                              root ? ctx->d_sh_root : NULL, st ) ) ) return rc;
+    HIPCHK( hipMemcpyAsync( out + done, ctx->d_sh_out, n, hipMemcpyDeviceToHost, st ), -2 );
+    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, ctx->d_sh_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
+    if( stream_wait( ctx, st, 1 ) ) return -2;
+    done += n;
+  }
+  return 0;
+}
+
+/* ---- batch SHA-256 ---------------------------------------------------- */
+
+extern "C" int
+fdgpu_sha256_batch_device( unsigned char const * d_data, unsigned long const * d_off, unsigned int const * d_sz,
+                           unsigned long cnt, unsigned char * d_hash, void * stream ) {
+  if( !cnt ) return 0;
+  if( cnt >= (1UL<<31) ) { fd_err = "batch too large"; return -1; }
+  unsigned g = (unsigned)( (cnt + FD_WG - 1) / FD_WG );
+  hipLaunchKernelGGL( fd_sha256_batch_kernel, dim3(g), dim3(FD_WG), 0, (hipStream_t)stream, d_data, d_off, d_sz,
+                      (u32)cnt, (uint4 *)d_hash );
+  HIPCHK( hipGetLastError(), -3 );
+  return 0;
+}
+
+extern "C" int
+fdgpu_sha256_batch_host( int device, unsigned char const * data, unsigned long data_sz, unsigned long const * off,
+                         unsigned int const * sz, unsigned long cnt, unsigned char * hash ) {
+  if( !cnt ) return 0;
+  for( unsigned long t=0; t<cnt; t++ )
+    if( off[t] > data_sz || sz[t] > data_sz - off[t] || sz[t] >= ( 1U << 29 ) ) { fd_err = "message out of buffer"; return -1; }
+  HIPCHK( hipSetDevice( device ), -2 );
+  unsigned char * d_data = NULL, * d_hash = NULL; unsigned long * d_off = NULL; unsigned int * d_sz = NULL;
+  size_t slack = 128;                                   /* fd_sha256_bytes reads up to 67 bytes past a message */
+  int rc = -2;
+  if( hipMalloc( (void **)&d_data, data_sz + slack ) != hipSuccess ||
+      hipMalloc( (void **)&d_off, cnt * sizeof(unsigned long) ) != hipSuccess ||
+      hipMalloc( (void **)&d_sz, cnt * sizeof(unsigned int) ) != hipSuccess ||
+      hipMalloc( (void **)&d_hash, cnt * 32UL ) != hipSuccess ) { fd_err = "hipMalloc failed"; goto done; }
+  if( hipMemset( d_data + data_sz, 0, slack ) != hipSuccess ||
+      ( data_sz && hipMemcpy( d_data, data, data_sz, hipMemcpyHostToDevice ) != hipSuccess ) ||
+      hipMemcpy( d_off, off, cnt * sizeof(unsigned long), hipMemcpyHostToDevice ) != hipSuccess ||
+      hipMemcpy( d_sz, sz, cnt * sizeof(unsigned int), hipMemcpyHostToDevice ) != hipSuccess ) { fd_err = "upload failed"; goto done; }
+  rc = fdgpu_sha256_batch_device( d_data, d_off, d_sz, cnt, d_hash, NULL );
+  if( !rc && hipMemcpy( hash, d_hash, cnt * 32UL, hipMemcpyDeviceToHost ) != hipSuccess ) { fd_err = "download failed"; rc = -2; }
+done:
+  hipFree( d_data ); hipFree( d_off ); hipFree( d_sz ); hipFree( d_hash );
+  return rc;
 }
 
 /* ---- batch SHA-512 ---------------------------------------------------- */

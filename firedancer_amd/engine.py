@@ -41,6 +41,12 @@ FDGPU_ERR_PARSE = -16
 FDGPU_ERR_OVERRUN = -17
 FDGPU_ERR_DESC = -18
 FDGPU_MSG_MAX = 65439
+SHRED_DESC_DTYPE = np.dtype([("off", "<u4"), ("sz", "<u2"), ("key_idx", "<u2"), ("sig_idx", "<u4"), ("flags", "<u4")])
+assert SHRED_DESC_DTYPE.itemsize == 16
+FDGPU_ERR_SHRED_PARSE = -19
+FDGPU_ERR_SHRED_MERKLE = -20
+FDGPU_SHRED_NO_SIG = 0xFFFF
+FDGPU_SHRED_STRICT_LEAF = 1
 ARENA_SLACK = 512            # readable bytes every device arena has behind its last byte
 TXN_IMG_STRIDE = 864
 
@@ -61,6 +67,8 @@ EXPORTS = ("fd_ed25519_verify", "fd_ed25519_verify_batch_single_msg", "fd_ed2551
            "fdgpu_ed25519_submit_raw_gather_dev_f", "fdgpu_launcher_new", "fdgpu_launcher_delete", "fdgpu_launcher_stats", "fdgpu_ed25519_set_launcher",
            "fdgpu_ed25519_submit_raw_gather_to", "fdgpu_ed25519_set_dedup_seeds", "fdgpu_ed25519_debug_fail_launch",
            "fdgpu_ed25519_sigs_prepare", "fdgpu_ed25519_verify_sigs_device", "fdgpu_ed25519_verify_sigs_host",
+           "fdgpu_ed25519_shreds_prepare", "fdgpu_ed25519_verify_shreds_device", "fdgpu_ed25519_verify_shreds_host",
+           "fdgpu_sha256_batch_device", "fdgpu_sha256_batch_host",
            "fdgpu_last_error")
 
 _lib = None
@@ -159,6 +167,21 @@ def load_library():
         L.fdgpu_ed25519_verify_sigs_host.restype = ctypes.c_int
         L.fdgpu_ed25519_verify_sigs_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
                                                     ctypes.c_ulong, ctypes.c_void_p]
+        L.fdgpu_ed25519_shreds_prepare.restype = ctypes.c_int
+        L.fdgpu_ed25519_shreds_prepare.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_ulong]
+        L.fdgpu_ed25519_verify_shreds_device.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_shreds_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                        ctypes.c_ulong, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong,
+                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_ed25519_verify_shreds_host.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_shreds_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                      ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                      ctypes.c_void_p]
+        L.fdgpu_sha256_batch_device.restype = ctypes.c_int
+        L.fdgpu_sha256_batch_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_sha256_batch_host.restype = ctypes.c_int
+        L.fdgpu_sha256_batch_host.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p]
         L.fdgpu_ed25519_faulted.restype = ctypes.c_int
         L.fdgpu_ed25519_faulted.argtypes = [ctypes.c_void_p]
         L.fdgpu_ed25519_debug_fault.argtypes = [ctypes.c_void_p]
@@ -308,6 +331,32 @@ def sha512_batch(msgs, device: int = 0) -> list[bytes]:
     if rc:
         raise RuntimeError(f"fdgpu_sha512_batch_host: {rc} {last_error()}")
     return [out[i].tobytes() for i in range(len(msgs))]
+
+
+def sha256_batch_host(msgs, device: int = 0) -> list[bytes]:
+    """SHA-256 of each message on the GPU (fdgpu_sha256_batch_host)."""
+    L = load_library()
+    off = np.zeros(len(msgs), np.uint64)
+    sz = np.zeros(len(msgs), np.uint32)
+    pos = 0
+    for i, m in enumerate(msgs):
+        off[i], sz[i] = pos, len(m)
+        pos += len(m)
+    data = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", np.uint8)
+    out = np.zeros((len(msgs), 32), np.uint8)
+    rc = L.fdgpu_sha256_batch_host(device, data.ctypes.data, pos, off.ctypes.data, sz.ctypes.data, len(msgs),
+                                   out.ctypes.data)
+    if rc:
+        raise RuntimeError(f"fdgpu_sha256_batch_host: {rc} {last_error()}", rc)
+    return [out[i].tobytes() for i in range(len(msgs))]
+
+
+def sha256_batch_device(d_data: int, d_off: int, d_sz: int, cnt: int, d_hash: int, stream: int | None = None) -> None:
+    """fdgpu_sha256_batch_device over raw device pointers: d_off u64 and d_sz u32 per message, 32 bytes a message to
+    d_hash (16-byte aligned); d_data has 128 readable bytes behind its last message."""
+    rc = load_library().fdgpu_sha256_batch_device(d_data, d_off, d_sz, cnt, d_hash, stream)
+    if rc:
+        raise RuntimeError(f"fdgpu_sha256_batch_device: {rc} {last_error()}", rc)
 
 
 def raw_records(payload: np.ndarray, off: np.ndarray, sz: np.ndarray):
@@ -471,6 +520,50 @@ class Engine:
         rc = self.L.fdgpu_ed25519_verify_sigs_device(self.ctx, d_arena, arena_sz, d_desc, cnt, msg_bytes, d_out, stream)
         if rc:
             raise RuntimeError(f"fdgpu_ed25519_verify_sigs_device: {rc} {last_error()}", rc)
+
+    # -- Merkle shreds: SHA-256 root, then the leader's signature ---------------
+    def shreds_prepare(self, max_shreds: int, max_keys: int = 1) -> None:
+        """fdgpu_ed25519_shreds_prepare: the device buffers of verify_shreds_device and verify_shreds_host.  Raises
+        on a refusal, with the C return value as the exception's second argument."""
+        rc = self.L.fdgpu_ed25519_shreds_prepare(self.ctx, max_shreds, max_keys)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_shreds_prepare: {rc} {last_error()}", rc)
+
+    def verify_shreds_host(self, arena: np.ndarray, desc: np.ndarray, keys=b"", arena_sz: int | None = None,
+                           want_root: bool = True):
+        """(codes, roots) of the Merkle shreds that desc (SHRED_DESC_DTYPE) names inside the first arena_sz bytes of
+        arena, a uint8 array: the code is FDGPU_ERR_DESC / FDGPU_ERR_SHRED_PARSE / FDGPU_ERR_SHRED_MERKLE, else 0
+        for a record whose key_idx is FDGPU_SHRED_NO_SIG, else fd_ed25519_verify of the derived root under key
+        key_idx of keys (32 bytes each: bytes or a uint8 array).  roots is (n, 32) uint8, zero for a flagged
+        record, or None with want_root = False.  sig_idx is computed by the call.  Synchronous.  arena_sz defaults
+        to the array less ARENA_SLACK bytes: if all of that lies in a registered region (host_register) the GPU
+        reads the shreds in place.  Raises on a refusal, with the C return value as the exception's second argument."""
+        if arena_sz is None:
+            arena_sz = arena.nbytes - ARENA_SLACK
+        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and 0 <= arena_sz <= arena.nbytes
+        desc = np.ascontiguousarray(desc, dtype=SHRED_DESC_DTYPE)
+        k = np.frombuffer(bytes(keys) + b"\0", np.uint8) if not isinstance(keys, np.ndarray) else \
+            np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        key_cnt = (len(k) - (0 if isinstance(keys, np.ndarray) else 1)) // 32
+        out = np.zeros(max(len(desc), 1), np.int8)
+        root = np.zeros((max(len(desc), 1), 32), np.uint8) if want_root else None
+        rc = self.L.fdgpu_ed25519_verify_shreds_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
+                                                     k.ctypes.data, key_cnt, out.ctypes.data,
+                                                     root.ctypes.data if want_root else None)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_shreds_host: {rc} {last_error()}", rc)
+        return out[:len(desc)], (root[:len(desc)] if want_root else None)
+
+    def verify_shreds_device(self, d_arena: int, arena_sz: int, d_desc: int, cnt: int, sig_cnt: int, d_keys: int,
+                             key_cnt: int, d_out: int, d_root: int | None = None, stream: int | None = None) -> None:
+        """Enqueue a batch of shred descriptors resident in device memory (raw device pointers; d_arena has
+        ARENA_SLACK readable bytes behind arena_sz, d_keys and d_root are 16-byte aligned, d_root may be None).
+        The caller numbers the signature-checked records, sig_idx in [0, sig_cnt).  Raises on a refusal, with the C
+        return value as the second argument."""
+        rc = self.L.fdgpu_ed25519_verify_shreds_device(self.ctx, d_arena, arena_sz, d_desc, cnt, sig_cnt, d_keys, key_cnt,
+                                                       d_out, d_root, stream)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_shreds_device: {rc} {last_error()}", rc)
 
     # -- raw payloads: device fd_txn_parse + verify ---------------------------
     def verify_raw_host(self, payload: np.ndarray, off: np.ndarray, sz: np.ndarray, want_img: bool = False):

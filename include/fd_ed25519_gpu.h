@@ -258,7 +258,8 @@ fdgpu_ed25519_verify_many_host( fdgpu_ed25519_ctx_t *         ctx,
 /* Signatures verified where they lie, from per-signature descriptors
    (the callers of SURVEY.md §3 D whose signatures are not
    shaped like a transaction: CRDS values inside a gossip packet, a prune's
-   two signable forms, pings and pongs, precompiles, repair and shreds).
+   two signable forms, pings and pongs, precompiles and repair; a Merkle
+   shred's signed message is not in the packet: the shreds calls below).
    Record i is the triple at byte offsets sig_off (64 bytes, R || S),
    pub_off (32 bytes) and msg_off (msg_sz bytes) of one arena of arena_sz
    bytes.  The offsets need no alignment and the ranges of one record, or
@@ -349,6 +350,141 @@ fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t *    ctx,
                                 fdgpu_sig_desc_t const * desc,
                                 unsigned long            cnt,
                                 signed char *            out );
+
+/* Merkle shreds: the one caller of SURVEY.md §3 D whose signed
+   message is not in the packet.  A shred's leader signs the root of its FEC
+   set's Merkle tree, and every verifier derives that root from the shred
+   and the proof it carries -- a SHA-256 over about 1.1 KB and one two-block
+   SHA-256 per proof level -- before one fd_ed25519_verify( root, 32,
+   shred->signature, leader ): src/disco/shred/fd_fec_resolver.c:386-476,
+   src/choreo/eqvoc/fd_eqvoc.c:270-289 through fd_shred_merkle_root, and
+   the repair path.  These calls do the hashing on the GPU.
+
+   Record i is the shred of sz bytes at arena + off (any alignment; sz is
+   fd_shred_parse's sz, the bytes available there).  out[i] is the first of
+     FDGPU_ERR_DESC          off + sz > arena_sz (in 64 bits), key_idx neither
+                             FDGPU_SHRED_NO_SIG nor below key_cnt, or a key
+                             named and sig_idx >= sig_cnt;
+     FDGPU_ERR_SHRED_PARSE   fd_shred_parse( shred, sz ) == NULL, or a legacy
+                             variant (0xa5, 0x5a), which parses and which the
+                             callers above reject (fd_fec_resolver.c:360-363);
+     FDGPU_ERR_SHRED_MERKLE  fd_shred_merkle_root would return 0 on a fresh
+                             tree: proof depth >= 10 or leaf index > 511;
+                             with FDGPU_SHRED_STRICT_LEAF in flags also leaf
+                             index >= 2^depth (fd_fec_resolver.c:412);
+   that applies (firedancer_amd/csrc/fd_shred_desc.h has the rules as code),
+   else FD_ED25519_SUCCESS for a record without a key, else
+   fd_ed25519_verify( root, 32, shred, keys + 32 key_idx ) under the
+   context's semantics.  root[32 i, 32 i + 32) gets the root fd_shred_merkle_
+   root derives, or 32 zero bytes for a record with one of the three codes
+   above.  A bad descriptor causes no load outside the arena and its slack
+   and changes no other record's code.
+
+   Many shreds carry one signature (every shred of a FEC set does), so a
+   record names a key only where the caller wants a signature checked: the
+   signature-checked records of a batch are numbered by the caller, sig_idx
+   in [0, sig_cnt), as fdgpu_txn_desc_t.sig_base numbers signatures.  The GPU
+   writes each as the one-signer transaction sig | key | root (128 bytes)
+   into slot sig_idx of the context's pack and hands the sig_cnt slots to the
+   verify kernels of the other batch calls, unchanged; pinned keys
+   (fdgpu_ed25519_set_pinned_keys) work as they do there.  A slot that no
+   good record names is 96 zero bytes with an empty message, verified and
+   not read.  Two records naming one sig_idx is the caller's error: the slot
+   holds one of them or a mix of both, both records get that slot's code,
+   and nothing else is harmed.  sig_cnt = 0 runs no verify kernel
+   (FDGPU_PATH_NONE). */
+#define FDGPU_ERR_SHRED_PARSE   (-19)
+#define FDGPU_ERR_SHRED_MERKLE  (-20)
+#define FDGPU_SHRED_NO_SIG      (0xFFFFu)   /* key_idx: derive the root only */
+#define FDGPU_SHRED_STRICT_LEAF (1u)        /* flags */
+
+typedef struct fdgpu_shred_desc {           /* 16 bytes */
+  unsigned int   off;      /* byte offset of the shred in the arena, any alignment */
+  unsigned short sz;       /* bytes available there (fd_shred_parse's sz) */
+  unsigned short key_idx;  /* leader key in keys[], or FDGPU_SHRED_NO_SIG */
+  unsigned int   sig_idx;  /* index among the batch's signature-checked shreds, given by the caller
+                              as fdgpu_txn_desc_t.sig_base is; ignored for NO_SIG */
+  unsigned int   flags;
+} fdgpu_shred_desc_t;
+
+/* fdgpu_ed25519_shreds_prepare: allocate what the two calls below need, all
+   of it device memory: 50 bytes per shred of max_shreds (descriptor, flag,
+   code and root), 145 bytes per signature slot (the 128-byte slot, its
+   fdgpu_txn_desc_t and its code) for min( max_sig, max_txn, max_shreds,
+   2^24 ) slots, 32 bytes per key of max_keys (<= 65,535), and 1 KiB of
+   slack.  A control-plane call like fdgpu_ed25519_sigs_prepare: it waits for
+   the device; a call that asks for no more than is there changes nothing, a
+   larger one reallocates.  0, -1 bad arguments, -2 the allocation failed
+   (the context is then unprepared), -3 faulted. */
+int
+fdgpu_ed25519_shreds_prepare( fdgpu_ed25519_ctx_t * ctx,
+                              unsigned long         max_shreds,
+                              unsigned long         max_keys );
+
+/* Device form.  d_arena (HBM, or the device view of a registered host
+   region) has 512 readable bytes after arena_sz; d_desc, d_keys (32 bytes a
+   key, 16-byte aligned), d_out (cnt codes) and d_root (32 cnt bytes, 16-byte
+   aligned, or NULL: no roots wanted) are device memory.  Asynchronous on
+   `stream` (NULL = the ctx's own), one batch of the context at a time.  -1
+   (nothing launched) if cnt exceeds max_shreds, sig_cnt the signature slots
+   (so max_sig and max_txn) or key_cnt max_keys as prepared; -3 on a faulted
+   or unprepared context. */
+int
+fdgpu_ed25519_verify_shreds_device( fdgpu_ed25519_ctx_t *      ctx,
+                                    unsigned char const *      d_arena,
+                                    unsigned long              arena_sz,
+                                    fdgpu_shred_desc_t const * d_desc,
+                                    unsigned long              cnt,
+                                    unsigned long              sig_cnt,
+                                    unsigned char const *      d_keys,
+                                    unsigned long              key_cnt,
+                                    signed char *              d_out,
+                                    unsigned char *            d_root,
+                                    void *                     stream );
+
+/* Host form.  Synchronous; -1 while the async pipeline holds anything.
+   sig_idx is computed here from key_idx (the caller's values are ignored:
+   every record that names a key takes the next slot) and the records go in
+   chunks of at most max_shreds records and as many signatures as there are
+   slots.  If [arena, arena + arena_sz + 512) lies inside one registered
+   region the GPU reads the shreds in place; otherwise each shred's first
+   min( sz, 1228 ) bytes go through the staging slot at a 1,232-byte stride
+   with rewritten descriptors (needs a ctx with staging that holds at least
+   one shred).  Both branches give identical codes and roots.  root may be
+   NULL.  -1 if key_cnt exceeds max_keys, -3 on a faulted or unprepared
+   context. */
+int
+fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t *      ctx,
+                                  unsigned char const *      arena,
+                                  unsigned long              arena_sz,
+                                  fdgpu_shred_desc_t const * desc,
+                                  unsigned long              cnt,
+                                  unsigned char const *      keys,
+                                  unsigned long              key_cnt,
+                                  signed char *              out,
+                                  unsigned char *            root );
+
+/* Batch SHA-256, the sibling of the SHA-512 calls below: hash[32 t, 32 t +
+   32) = SHA-256 of the sz[t] < 2^29 bytes at data + off[t] (any alignment).
+   The device form reads up to 67 bytes past each message, so d_data must
+   carry 128 readable bytes of slack after its last message; d_hash is
+   16-byte aligned.  The host form copies, runs on `device` and waits. */
+int
+fdgpu_sha256_batch_device( unsigned char const * d_data,
+                           unsigned long const * d_off,
+                           unsigned int const *  d_sz,
+                           unsigned long         cnt,
+                           unsigned char *       d_hash,
+                           void *                stream );
+
+int
+fdgpu_sha256_batch_host( int                   device,
+                         unsigned char const * data,
+                         unsigned long         data_sz,
+                         unsigned long const * off,
+                         unsigned int const *  sz,
+                         unsigned long         cnt,
+                         unsigned char *       hash );
 
 /* fdgpu_ed25519_verify_txn_ptrs: out[i] = the fd_ed25519_verify_batch_
    single_msg code of transaction i, whose payload is at payloads[i] (any
