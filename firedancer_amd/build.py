@@ -15,7 +15,7 @@ ARCH = os.environ.get("FDGPU_ARCH", "gfx950")
 
 HIP_SRCS = ["fd_ed25519_gpu.hip"]
 HIP_DEPS = ["fd_gpu_f25519.h", "fd_gpu_sha512.h", "fd_gpu_sha256.h", "fd_gpu_curve.h", "fd_gpu_txn.h", "fd_gpu_lattice.h",
-            "fd_pin_list.h", "fd_sig_desc.h", "fd_shred_desc.h", "../../include/fd_ed25519_gpu.h"]
+            "fd_pin_list.h", "fd_sig_desc.h", "fd_shred_desc.h", "fd_fec_desc.h", "../../include/fd_ed25519_gpu.h"]
 
 
 def _stale(out: str, deps: list[str]) -> bool:
@@ -86,9 +86,20 @@ def build_shred_desc_check(force: bool = False) -> str:
     return out
 
 
+def build_fec_desc_check(force: bool = False) -> str:
+    """fd_fec_desc_check: the stand-alone host program that checks fd_fec_desc.h's rules at their edges and the tree's
+    shape for every leaf count (tests/test_fec_desc.py runs it; it prints "ok")."""
+    out = os.path.join(PKG, "fd_fec_desc_check")
+    if force or _stale(out, ["fd_fec_desc_check.c", "fd_fec_desc.h", "fd_shred_desc.h"]):
+        subprocess.run(["gcc", "-std=gnu11", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-o", out,
+                        os.path.join(CSRC, "fd_fec_desc_check.c")], check=True)
+    return out
+
+
 def build_all(force: bool = False) -> None:
     build_synth(force)
     build_shred_desc_check(force)
+    build_fec_desc_check(force)
     build_lattice_host(force)
     build_engine(force)
     build_vtile(force)

@@ -3543,6 +3543,260 @@ fd_shred_flag_kernel( fdgpu_shred_desc_t const * __restrict__ desc, u32 n, i8 co
   out[i] = f;
 }
 
+/* FEC sets (fdgpu_ed25519_verify_fec_sets_device / _host): a complete set's whole tree -- n leaves, the
+   n - 1 or so merges over them, the root and a proof for every leaf -- where fd_shred_root_kernel walks one proof
+   per shred.  fd_fec_desc.h has the tree's shape and the rules that decide a set's code, shared with the host.
+
+   fd_fec_tree_kernel  one workgroup per set, lane j its leaf j; the block is sized for the batch's largest set, so
+                       lanes at or past cnt only keep the barriers.  Every loop around a barrier runs to a bound the
+                       whole block shares (D, from the descriptor and the agreed code).  The device form cannot see the
+                       descriptors: past the set count at which every block is resident at once it launches once per
+                       block size (64, 128, 192, 256 lanes, as far as member_cnt allows) and each launch takes the sets
+                       of its size, so that no set waits in a block four times its own (fec_launch).
+     phase 0  each lane loads its member's header words, signature and chained root; member 0's go to LDS, the first
+              code member is found with an LDS min; then every lane holds its member against them and the set's code
+              (descriptor, member) is or-ed together in LDS.  A set with a code hashes nothing.
+     phase 1  the leaf: fd_sha256_shred_leaf, its first 20 bytes to layer 0 in LDS
+     phase 2  for l < D: barrier, lanes below ceil( n_l / 2 ) merge nodes 2j and min( 2j + 1, n_l - 1 ) into layer
+              l + 1.  All layers stay: at most 510 nodes of 5 words for 256 leaves (an odd stride: a layer's stores fall
+              on distinct banks; the reads at stride 10 pair up two lanes to a bank) and the root's 8 words; the LDS
+              is sized by the block, 3.2 KB at 64 lanes and 11.6 KB at 256.
+     phase 3  barrier; each lane compares its D proof nodes with what its shred carries (CHECK_PROOFS, not FILL),
+              lane 0 the root with the expected one; barrier; then FILL lanes store their proofs where the shreds lie
+              and lane 0 the root, the code and, for a keyed set, sig | key | root to its slot.
+   fd_fec_flag_kernel  behind the batch: out[i] = the set's code, else 0 without a key, else its slot's code
+
+   No load leaves the arena and its slack: a member is looked at only if off + 1203 <= arena_sz, a code shred only
+   if off + 1228 <= arena_sz; the leaf reads at most 67 bytes past moff <= 1228.  Stores go to the proofs of FILL
+   members of good sets only. */
+#include "fd_fec_desc.h"
+
+#define FD_FEC_WG_MAX 256
+/* words of LDS a block of `lanes` lanes needs: the layers under the root (fd_fec_node_cap nodes of 5 words), the root,
+   member 0 (header words, chained root, signature: 31, padded), a word per lane, three shared words (padded) */
+#define FD_FEC_LDS_WORDS( lanes ) ( 5u * fd_fec_node_cap( lanes ) + 8u + 32u + (lanes) + 4u )
+
+__global__ void __launch_bounds__( FD_FEC_WG_MAX )
+fd_fec_tree_kernel( unsigned char * arena, unsigned long arena_sz, fdgpu_fec_desc_t const * __restrict__ desc,
+                    fdgpu_fec_member_t const * __restrict__ member, u32 nmember, u32 nsig,
+                    uint4 const * __restrict__ keys, u32 nkey, uint4 const * __restrict__ expect,
+                    uint4 * __restrict__ pack, fdgpu_txn_desc_t * __restrict__ tdesc, i8 * __restrict__ flag,
+                    uint4 * __restrict__ root, u32 only ) {
+  extern __shared__ __attribute__(( aligned( 16 ) )) u32 fd_fec_lds[];
+  u32 * node = fd_fec_lds;                                   /* the layers under the root, 5 words a node */
+  u32 * top  = node + 5u * fd_fec_node_cap( blockDim.x );    /* the root */
+  u32 * m0   = top + 8;                                      /* member 0: header words, chained root, signature */
+  u32 * cc   = m0 + 32;                                      /* data_cnt | code_cnt << 16 as each member has them */
+  u32 * sh3  = cc + blockDim.x;
+  u32 & first_code = sh3[0], & st0 = sh3[1], & st1 = sh3[2];
+  u32 i = blockIdx.x, j = threadIdx.x;
+  fdgpu_fec_desc_t d = desc[i];
+  u32 n = d.cnt;
+  int set_bad = fd_fec_set_bad( d.member0, n, d.key_idx, d.sig_idx, nmember, nkey, nsig );
+  /* a launch for one block size (only = lanes / 64) takes the sets that fill it, and the bad ones with the smallest:
+     the whole block leaves here, in front of every barrier */
+  if( only && ( set_bad ? 1u : ( n + 63u ) >> 6 ) != only ) return;
+  set_bad |= n > blockDim.x;
+  if( set_bad ) n = 0u;
+  u32 D = n ? fd_fec_depth( n ) : 0u;
+
+  /* phase 0 */
+  if( j == 0u ) { first_code = ~0u; st0 = 0u; st1 = 0u; }
+  int live = j < n, rbad = 0, cls = 1;
+  fdgpu_fec_member_t m = { 0u, 0u };
+  unsigned char * sh = arena;
+  u32 w[ FD_SHRED_FIELD_WORDS ], ch[ 8 ], sg[ 16 ];
+#pragma unroll
+  for( int k=0; k<FD_SHRED_FIELD_WORDS; k++ ) w[k] = 0u;
+#pragma unroll
+  for( int k=0; k<8; k++ ) ch[k] = 0u;
+#pragma unroll
+  for( int k=0; k<16; k++ ) sg[k] = 0u;
+  fd_shred_fields_t f = {};
+  fd_shred_info_t in = { 0U, 0U, 0U };
+  u32 type = 0u;
+  if( live ) {
+    m    = member[ (size_t)d.member0 + j ];
+    sh   = arena + m.off;
+    rbad = fd_fec_range_bad( m.off, arena_sz, 0, 0u );
+    if( !rbad ) {
+      fd_load_words<FD_SHRED_FIELD_WORDS>( w, sh + 64 );
+      rbad = fd_fec_range_bad( m.off, arena_sz, 1, w[0] & 0xffu );
+    }
+    if( !rbad ) {
+      fd_shred_fields( w, &f );
+      type = (u32)f.variant & 0xf0u;
+      cls  = fd_shred_classify( &f, fd_shred_is_code( type ) ? FD_SHRED_CODE_SZ : FD_SHRED_DATA_SZ, FD_SHRED_STRICT_LEAF, &in );
+      if( !cls ) {
+        fd_load_words<16>( sg, sh );
+        if( fd_shred_is_chained( type ) ) fd_load_words<8>( ch, sh + in.moff - 32u );
+      }
+    }
+  }
+  __syncthreads();
+  if( live ) {
+    cc[j] = (u32)f.h53 | ( (u32)f.h55 << 16 );
+    if( rbad ) atomicOr( &st0, 1u );
+    else if( fd_shred_is_code( type ) ) atomicMin( &first_code, j );
+  }
+  if( j == 0u ) {
+#pragma unroll
+    for( int k=0; k<FD_SHRED_FIELD_WORDS; k++ ) m0[k] = w[k];
+#pragma unroll
+    for( int k=0; k<8; k++ ) m0[ 7+k ] = ch[k];
+#pragma unroll
+    for( int k=0; k<16; k++ ) m0[ 15+k ] = sg[k];
+  }
+  __syncthreads();
+  if( live & !rbad ) {
+    u32 w0[ FD_SHRED_FIELD_WORDS ], c0[ 8 ], s0[ 16 ];
+#pragma unroll
+    for( int k=0; k<FD_SHRED_FIELD_WORDS; k++ ) w0[k] = m0[k];
+#pragma unroll
+    for( int k=0; k<8; k++ ) c0[k] = m0[ 7+k ];
+#pragma unroll
+    for( int k=0; k<16; k++ ) s0[k] = m0[ 15+k ];
+    fd_shred_fields_t f0 = {}, fc = f;
+    fd_shred_fields( w0, &f0 );
+    u32 fci = first_code;
+    if( fci < n ) { u32 c = cc[ fci ]; fc.h53 = (unsigned short)( c & 0xffffu ); fc.h55 = (unsigned short)( c >> 16 ); }
+    int bad = fd_fec_member_bad( &f, fd_fec_version( w ), &f0, fd_fec_version( w0 ), &fc, j, n, &in );
+    if( !bad ) {
+      if( fd_shred_is_chained( type ) ) bad = fd_fec_words_differ( ch, c0, 8U );
+      bad |= fd_fec_words_differ( sg, s0, 16U );
+    }
+    if( bad ) atomicOr( &st0, 2u );
+  }
+  __syncthreads();
+  u32 agreed = st0;
+  int code = ( set_bad | (int)( agreed & 1u ) ) ? FD_SHRED_ERR_DESC : ( ( agreed & 2u ) ? FD_FEC_ERR_MEMBER : 0 );
+  if( code ) D = 0u;                                           /* (the whole block: no merge, no proof) */
+
+  /* phase 1 */
+  if( !code && live ) {
+    u32 h[8];
+    fd_sha256_shred_leaf( h, sh + 64, in.moff - 64u );
+#pragma unroll
+    for( int k=0; k<5; k++ ) node[ 5u*j + (u32)k ] = h[k];
+    if( n == 1u ) {
+#pragma unroll
+      for( int k=0; k<8; k++ ) top[k] = h[k];
+    }
+  }
+
+  /* phase 2 */
+  u32 base = 0u, nl = n;
+#pragma unroll 1
+  for( u32 l=0u; l<D; l++ ) {
+    __syncthreads();
+    u32 nn = ( nl + 1u ) >> 1;
+    if( j < nn ) {
+      u32 a = base + 2u*j, b = base + ( 2u*j + 1u < nl ? 2u*j + 1u : nl - 1u );
+      u32 x[8], s[5];
+#pragma unroll
+      for( int k=0; k<5; k++ ) { x[k] = node[ 5u*a + (u32)k ]; s[k] = node[ 5u*b + (u32)k ]; }
+      fd_sha256_shred_merge( x, s, 0 );
+      if( l + 1u == D ) {
+#pragma unroll
+        for( int k=0; k<8; k++ ) top[k] = x[k];
+      } else {
+#pragma unroll
+        for( int k=0; k<5; k++ ) node[ 5u*( base + nl + j ) + (u32)k ] = x[k];
+      }
+    }
+    base += nl; nl = nn;
+  }
+
+  /* phase 3 */
+  __syncthreads();
+  int fill = ( m.flags & FD_FEC_FILL ) != 0u;
+  if( !code && live && ( d.flags & FD_FEC_CHECK_PROOFS ) && !fill ) {
+    u32 differ = 0u;
+    base = 0u;
+#pragma unroll 1
+    for( u32 l=0u; l<D; l++ ) {
+      u32 sib = base + fd_fec_sibling( j, l, n );
+      u32 c[5];
+      fd_load_words<5>( c, sh + in.moff + FD_SHRED_NODE_SZ * l );
+#pragma unroll
+      for( int k=0; k<5; k++ ) differ |= fd_bswap32( c[k] ) ^ node[ 5u*sib + (u32)k ];
+      base += fd_fec_layer_cnt( n, l );
+    }
+    if( differ ) atomicOr( &st1, 2u );
+  }
+  u32 r[8];
+#pragma unroll
+  for( int k=0; k<8; k++ ) r[k] = 0u;
+  if( !code && j == 0u ) {
+#pragma unroll
+    for( int k=0; k<8; k++ ) r[k] = fd_bswap32( top[k] );      /* the root's bytes as little-endian words */
+    if( d.flags & FD_FEC_CHECK_ROOT ) {
+      u32 differ = 1u;                                         /* (nothing to hold it against: not the root) */
+      if( expect ) {
+        uint4 e0 = expect[ 2UL*i ], e1 = expect[ 2UL*i + 1UL ];
+        differ = ( e0.x ^ r[0] ) | ( e0.y ^ r[1] ) | ( e0.z ^ r[2] ) | ( e0.w ^ r[3] )
+               | ( e1.x ^ r[4] ) | ( e1.y ^ r[5] ) | ( e1.z ^ r[6] ) | ( e1.w ^ r[7] );
+      }
+      if( differ ) atomicOr( &st1, 1u );
+    }
+  }
+  __syncthreads();
+  agreed = st1;
+  if( !code ) code = ( agreed & 1u ) ? FD_FEC_ERR_ROOT : ( ( agreed & 2u ) ? FD_FEC_ERR_PROOF : 0 );
+  if( !code && live && fill ) {
+    base = 0u;
+#pragma unroll 1
+    for( u32 l=0u; l<D; l++ ) {
+      u32 sib = base + fd_fec_sibling( j, l, n );
+      u32 s[5];
+#pragma unroll
+      for( int k=0; k<5; k++ ) s[k] = node[ 5u*sib + (u32)k ];
+      unsigned char * p = sh + in.moff + FD_SHRED_NODE_SZ * l;
+      if( !( (uintptr_t)p & 3UL ) ) {
+#pragma unroll
+        for( int k=0; k<5; k++ ) ( (u32 *)p )[k] = fd_bswap32( s[k] );
+      } else {
+#pragma unroll
+        for( int k=0; k<20; k++ ) p[k] = (unsigned char)( s[ k >> 2 ] >> ( 24 - 8*( k & 3 ) ) );
+      }
+      base += fd_fec_layer_cnt( n, l );
+    }
+  }
+  if( j == 0u ) {
+    flag[i] = (i8)code;
+    if( root ) {                                               /* (a descriptor's or a member's code: 32 zero bytes) */
+      root[ 2UL*i     ] = make_uint4( r[0], r[1], r[2], r[3] );
+      root[ 2UL*i+1UL ] = make_uint4( r[4], r[5], r[6], r[7] );
+    }
+    if( !code && d.key_idx != FD_SHRED_NO_SIG ) {
+      uint4 const * k = keys + 2UL * d.key_idx;
+      uint4 k0 = k[0], k1 = k[1];
+      uint4 * p = pack + (size_t)d.sig_idx * ( FD_SHRED_SLOT / 16UL );
+      u32 s0[ 16 ];                                            /* (loaded again: not held through the hashes) */
+      fd_load_words<16>( s0, sh );
+#pragma unroll
+      for( int q=0; q<4; q++ ) p[q] = make_uint4( s0[4*q], s0[4*q+1], s0[4*q+2], s0[4*q+3] );
+      p[4] = k0; p[5] = k1;
+      p[6] = make_uint4( r[0], r[1], r[2], r[3] );
+      p[7] = make_uint4( r[4], r[5], r[6], r[7] );
+      fdgpu_txn_desc_t t;
+      t.payload_off = (u32)( FD_SHRED_SLOT * d.sig_idx ); t.sig_base = d.sig_idx; t.payload_sz = 128;
+      t.message_off = 96; t.acct_addr_off = 64; t.signature_off = 0; t.sig_cnt = 1;
+      tdesc[ d.sig_idx ] = t;
+    }
+  }
+}
+
+__global__ void __launch_bounds__( FD_WG )
+fd_fec_flag_kernel( fdgpu_fec_desc_t const * __restrict__ desc, u32 n, i8 const * __restrict__ flag,
+                    i8 const * __restrict__ code, i8 * __restrict__ out ) {
+  u32 i = blockIdx.x * FD_WG + threadIdx.x;
+  if( i >= n ) return;
+  i8 f = flag[i];
+  if( !f && desc[i].key_idx != FD_SHRED_NO_SIG ) f = code[ desc[i].sig_idx ];   /* (not flagged: sig_idx < sig_cnt) */
+  out[i] = f;
+}
+
 /* ==================================================================
    Host runtime: C ABI (include/fd_ed25519_gpu.h)
    ================================================================== */
@@ -3731,6 +3985,22 @@ struct fdgpu_ed25519_ctx {
   i8 *                d_sh_out;  /*   [sh_max] the host form's codes */
   unsigned char *     d_sh_root; /*   [32 sh_max] the host form's roots */
   unsigned char *     d_sh_keys; /*   [32 sh_keys] the host form's keys */
+  /* FEC sets (fdgpu_ed25519_fec_prepare): all device memory */
+  unsigned long       fc_sets;   /*   sets a batch may hold; 0 = unprepared */
+  unsigned long       fc_members;/*   members a batch may hold */
+  unsigned long       fc_keys;   /*   keys a batch may name */
+  unsigned long       fc_sig;    /*   signature slots: min( max_sig, max_txn, fc_sets ) */
+  unsigned long       fc_all;    /*   sets whose 256-lane blocks are all resident at once: 4 a CU (fd_fec_tree_kernel: 4 waves a SIMD) */
+  unsigned char *     d_fc_pack; /*   [128 fc_sig + 2 FD_ARENA_SLACK] the slots, sig | key | root */
+  fdgpu_txn_desc_t *  d_fc_tdesc;/*   [fc_sig] the slots as one-signer transactions */
+  i8 *                d_fc_code; /*   [fc_sig] the batch's code of each slot */
+  i8 *                d_fc_flag; /*   [fc_sets] a set's own code, 0 = none */
+  fdgpu_fec_desc_t *  d_fc_desc; /*   [fc_sets] the host form's uploaded descriptors */
+  fdgpu_fec_member_t * d_fc_member; /* [fc_members] the host form's uploaded members */
+  i8 *                d_fc_out;  /*   [fc_sets] the host form's codes */
+  unsigned char *     d_fc_root; /*   [32 fc_sets] the host form's roots */
+  unsigned char *     d_fc_expect; /* [32 fc_sets] the host form's expected roots */
+  unsigned char *     d_fc_keys; /*   [32 fc_keys] the host form's keys */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
@@ -5019,6 +5289,238 @@ fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const
     HIPCHK( hipMemcpyAsync( out + done, ctx->d_sh_out, n, hipMemcpyDeviceToHost, st ), -2 );
     if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, ctx->d_sh_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
     if( stream_wait( ctx, st, 1 ) ) return -2;
+    done += n;
+  }
+  return 0;
+}
+
+/* ---- FEC sets ----------------------------------------------- */
+
+extern "C" int
+fdgpu_ed25519_fec_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_sets, unsigned long max_members,
+                           unsigned long max_keys ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_fec_prepare: the context has faulted"; return -3; }
+  if( !max_sets || max_sets >= ( 1UL << 31 ) || !max_members || max_members >= ( 1UL << 31 ) ||
+      !max_keys || max_keys > (unsigned long)FD_SHRED_NO_SIG ) {
+    fd_err = "fdgpu_ed25519_fec_prepare: bad size"; return -1;
+  }
+  if( max_sets <= ctx->fc_sets && max_members <= ctx->fc_members && max_keys <= ctx->fc_keys ) return 0;
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  if( max_sets    < ctx->fc_sets    ) max_sets    = ctx->fc_sets;
+  if( max_members < ctx->fc_members ) max_members = ctx->fc_members;
+  if( max_keys    < ctx->fc_keys    ) max_keys    = ctx->fc_keys;
+  /* larger buffers: nothing of the context may still read the old ones */
+  HIPCHK( hipDeviceSynchronize(), -2 );
+  ctx->fc_sets = 0UL; ctx->fc_members = 0UL; ctx->fc_keys = 0UL; ctx->fc_sig = 0UL;
+  ctx_dev_free( ctx, &ctx->d_fc_pack ); ctx_dev_free( ctx, &ctx->d_fc_tdesc );  ctx_dev_free( ctx, &ctx->d_fc_code );
+  ctx_dev_free( ctx, &ctx->d_fc_flag ); ctx_dev_free( ctx, &ctx->d_fc_desc );   ctx_dev_free( ctx, &ctx->d_fc_member );
+  ctx_dev_free( ctx, &ctx->d_fc_out );  ctx_dev_free( ctx, &ctx->d_fc_root );   ctx_dev_free( ctx, &ctx->d_fc_expect );
+  ctx_dev_free( ctx, &ctx->d_fc_keys );
+  size_t ns = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
+  if( ns > max_sets ) ns = max_sets;
+  if( ns > ( 1UL << 24 ) ) ns = 1UL << 24;                   /* (128 ns + slack inside payload_off's 32 bits) */
+  size_t pack = FD_SHRED_SLOT * ns + 2UL * FD_ARENA_SLACK;
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_pack, pack ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_code, ns ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_flag, max_sets ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_desc, max_sets * sizeof(fdgpu_fec_desc_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_member, max_members * sizeof(fdgpu_fec_member_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_out, max_sets ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_root, 32UL * max_sets ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_expect, 32UL * max_sets ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_keys, 32UL * max_keys ), -2 );
+  HIPCHK( hipMemsetAsync( ctx->d_fc_pack, 0, pack, ctx->stream ), -2 );
+  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
+  int cus = 0;
+  HIPCHK( hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, ctx->device ), -2 );
+  ctx->fc_all = 4UL * (unsigned long)( cus > 0 ? cus : 1 );
+  ctx->fc_sets = max_sets; ctx->fc_members = max_members; ctx->fc_keys = max_keys; ctx->fc_sig = ns;
+  return 0;
+}
+
+/* the block that holds a set of most leaves: whole wavefronts */
+static unsigned
+fec_block( unsigned long most ) {
+  if( most > FD_FEC_LEAF_MAX ) most = FD_FEC_LEAF_MAX;
+  if( !most ) most = 1UL;
+  return (unsigned)( 64UL * ( ( most + 63UL ) / 64UL ) );
+}
+
+/* the kernels of one batch of sets on st: the slots, the trees, the batch over the slots, the codes */
+static int
+fec_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char * d_arena, unsigned long arena_sz, fdgpu_fec_desc_t const * d_desc,
+            unsigned long set_cnt, fdgpu_fec_member_t const * d_member, unsigned long member_cnt, unsigned long sig_cnt,
+            unsigned char const * d_keys, unsigned long key_cnt, unsigned char const * d_expect, i8 * d_out,
+            unsigned char * d_root, unsigned block, hipStream_t st ) {
+  if( sig_cnt )
+    hipLaunchKernelGGL( fd_shred_slot_kernel, dim3( (unsigned)( ( sig_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
+                        (uint4 *)ctx->d_fc_pack, ctx->d_fc_tdesc, (u32)sig_cnt );
+  /* block: the lanes that hold the largest set, known on the host; 0: not known (the descriptors are the device's).  A
+     good set has cnt <= member_cnt, which bounds the block.  While every block of that size is resident at once, one
+     launch: lanes without a leaf cost nothing then, and a block of four waves has one on each SIMD of its CU, where
+     one-wave blocks double up (measured: 0.40 against 0.47 ms at 1,024 sets of 64).  Beyond that, one launch per block
+     size, each taking the sets of its size (0.63 against 0.80 ms at 4,096). */
+  if( !block && set_cnt <= ctx->fc_all ) block = fec_block( member_cnt );
+  unsigned lo = block ? block : 64U, hi = block ? block : fec_block( member_cnt );
+  for( unsigned b=lo; b<=hi; b+=64U )
+    hipLaunchKernelGGL( fd_fec_tree_kernel, dim3( (unsigned)set_cnt ), dim3(b), 4U * FD_FEC_LDS_WORDS( b ), st, d_arena, arena_sz,
+                        d_desc, d_member, (u32)member_cnt, (u32)sig_cnt, (uint4 const *)d_keys, (u32)key_cnt,
+                        (uint4 const *)d_expect, (uint4 *)ctx->d_fc_pack, ctx->d_fc_tdesc, ctx->d_fc_flag, (uint4 *)d_root,
+                        block ? 0U : b / 64U );
+  HIPCHK( hipGetLastError(), -3 );
+  if( sig_cnt ) {
+    int rc = launch_batch( ctx, ctx->d_fc_pack, ctx->d_fc_tdesc, sig_cnt, sig_cnt, ctx->d_fc_code, NULL, st );
+    if( rc ) return rc;
+  } else ctx->last_path = FDGPU_PATH_NONE;                    /* a batch without signatures */
+  hipLaunchKernelGGL( fd_fec_flag_kernel, dim3( (unsigned)( ( set_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st, d_desc,
+                      (u32)set_cnt, (i8 const *)ctx->d_fc_flag, (i8 const *)ctx->d_fc_code, d_out );
+  HIPCHK( hipGetLastError(), -3 );
+  return 0;
+}
+
+extern "C" int
+fdgpu_ed25519_verify_fec_sets_device( fdgpu_ed25519_ctx_t * ctx, unsigned char * d_arena, unsigned long arena_sz,
+                                      fdgpu_fec_desc_t const * d_desc, unsigned long set_cnt,
+                                      fdgpu_fec_member_t const * d_member, unsigned long member_cnt, unsigned long sig_cnt,
+                                      unsigned char const * d_keys, unsigned long key_cnt, unsigned char const * d_expect,
+                                      signed char * d_out, unsigned char * d_root, void * stream ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_fec_sets_device: the context has faulted"; return -3; }
+  if( !ctx->fc_sets ) { fd_err = "fdgpu_ed25519_verify_fec_sets_device: no fdgpu_ed25519_fec_prepare"; return -3; }
+  if( set_cnt > ctx->fc_sets || member_cnt > ctx->fc_members || sig_cnt > ctx->fc_sig || key_cnt > ctx->fc_keys ) {
+    fd_err = "batch larger than prepared"; return -1;
+  }
+  if( !set_cnt ) return 0;
+  if( !d_arena || !d_desc || !d_out || ( member_cnt && !d_member ) || ( key_cnt && !d_keys ) ) { fd_err = "NULL argument"; return -1; }
+  if( ( (uintptr_t)d_keys | (uintptr_t)d_root | (uintptr_t)d_expect ) & 15UL ) {
+    fd_err = "d_keys, d_root and d_expect are 16-byte aligned"; return -1;
+  }
+  HIPCHK( hipSetDevice( ctx->device ), -2 );
+  return fec_launch( ctx, d_arena, arena_sz, d_desc, set_cnt, d_member, member_cnt, sig_cnt, d_keys, key_cnt, d_expect,
+                     (i8 *)d_out, d_root, 0U, stream ? (hipStream_t)stream : ctx->stream );
+}
+
+/* leaves of a set whose members the host form uploads: 0 for a set that is bad whatever its members are */
+static unsigned long
+fec_need( fdgpu_fec_desc_t const & d, unsigned long member_cnt ) {
+  if( !d.cnt || d.cnt > FD_FEC_LEAF_MAX || (unsigned long)d.member0 + (unsigned long)d.cnt > member_cnt ) return 0UL;
+  return (unsigned long)d.cnt;
+}
+
+extern "C" int
+fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t * ctx, unsigned char * arena, unsigned long arena_sz,
+                                    fdgpu_fec_desc_t const * desc, unsigned long set_cnt,
+                                    fdgpu_fec_member_t const * member, unsigned long member_cnt,
+                                    unsigned char const * keys, unsigned long key_cnt, unsigned char const * expect,
+                                    signed char * out, unsigned char * root ) {
+  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
+  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: the context has faulted"; return -3; }
+  if( !ctx->fc_sets ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: no fdgpu_ed25519_fec_prepare"; return -3; }
+  if( key_cnt > ctx->fc_keys ) { fd_err = "more keys than prepared"; return -1; }
+  if( !set_cnt ) return 0;
+  if( !arena || !desc || !out || ( member_cnt && !member ) || ( key_cnt && !keys ) ) { fd_err = "NULL argument"; return -1; }
+  int rc;
+  unsigned char * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
+  unsigned long most = ctx->fc_members;
+  if( !d_arena ) {
+    /* any other host memory: the members' shreds go through the staging slot, one every FD_SHRED_STRIDE bytes */
+    if( ( rc = sync_ctx( ctx, 1 ) ) ) return rc;
+    unsigned long fit = ctx->max_payload / FD_SHRED_STRIDE;
+    if( most > fit ) most = fit;
+  }
+  for( unsigned long s=0UL; s<set_cnt; s++ ) {
+    if( ( desc[s].flags & FD_FEC_CHECK_ROOT ) && !expect ) { fd_err = "FDGPU_FEC_CHECK_ROOT without expect"; return -1; }
+    if( fec_need( desc[s], member_cnt ) > most ) { fd_err = "a set holds more members than a batch may"; return -1; }
+  }
+  if( ( rc = sync_begin( ctx ) ) ) return rc;
+  hipStream_t st = ctx->stream;
+  fd_slot & sl = ctx->slot[0];
+  if( key_cnt ) HIPCHK( hipMemcpyAsync( ctx->d_fc_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
+  std::vector<fdgpu_fec_desc_t>   td;
+  std::vector<fdgpu_fec_member_t> tm;
+  std::vector<unsigned int>       from;                       /* staged: where member k's shred came from */
+  std::vector<i8>                 fl;
+  for( unsigned long done=0UL; done<set_cnt; ) {
+    /* the chunk: whole sets up to the prepared counts, signatures -- numbered here, in order -- up to the slots */
+    unsigned long n = 0UL, nm = 0UL, nsig = 0UL, big = 0UL;
+    int any_fill = 0;
+    td.clear(); tm.clear(); from.clear();
+    while( done + n < set_cnt && n < ctx->fc_sets ) {
+      fdgpu_fec_desc_t d = desc[ done + n ];
+      unsigned long need = fec_need( d, member_cnt );
+      if( nm + need > most ) break;
+      if( d.key_idx != FD_SHRED_NO_SIG ) {
+        if( nsig == ctx->fc_sig ) break;
+        d.sig_idx = (unsigned int)nsig++;
+      }
+      if( !need ) d.member0 = 0xFFFFFFFFU;                     /* stays bad */
+      else {
+        for( unsigned long j=0UL; j<need; j++ ) {
+          fdgpu_fec_member_t m = member[ (unsigned long)d.member0 + j ];
+          any_fill |= (int)( m.flags & FD_FEC_FILL );
+          if( !d_arena ) {
+            unsigned long k = nm + j;
+            from.push_back( m.off );
+            int bad = fd_fec_range_bad( m.off, arena_sz, 0, 0U );
+            if( !bad ) bad = fd_fec_range_bad( m.off, arena_sz, 1, arena[ (unsigned long)m.off + 0x40UL ] );
+            if( bad ) m.off = 0xFFFFFFFFU;                     /* stays bad */
+            else {
+              unsigned long sz = fd_shred_is_code( arena[ (unsigned long)m.off + 0x40UL ] & 0xf0U ) ? FD_SHRED_CODE_SZ : FD_SHRED_DATA_SZ;
+              memcpy( sl.h_payload + FD_SHRED_STRIDE * k, arena + m.off, sz );
+              m.off = (unsigned int)( FD_SHRED_STRIDE * k );
+            }
+          }
+          tm.push_back( m );
+        }
+        d.member0 = (unsigned int)nm;
+        nm += need;
+        if( need > big ) big = need;
+      }
+      td.push_back( d );
+      n++;
+    }
+    if( !n ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: no signature slot"; return -1; }
+    unsigned char * da = d_arena; unsigned long dsz = arena_sz;
+    if( !d_arena ) {
+      dsz = FD_SHRED_STRIDE * nm;
+      memset( sl.h_payload + dsz, 0, FD_ARENA_SLACK );
+      HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, dsz + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
+      da = sl.d_payload;
+    }
+    HIPCHK( hipMemcpyAsync( ctx->d_fc_desc, td.data(), n * sizeof(fdgpu_fec_desc_t), hipMemcpyHostToDevice, st ), -2 );
+    if( nm ) HIPCHK( hipMemcpyAsync( ctx->d_fc_member, tm.data(), nm * sizeof(fdgpu_fec_member_t), hipMemcpyHostToDevice, st ), -2 );
+    if( expect ) HIPCHK( hipMemcpyAsync( ctx->d_fc_expect, expect + 32UL * done, 32UL * n, hipMemcpyHostToDevice, st ), -2 );
+    if( ( rc = fec_launch( ctx, da, dsz, ctx->d_fc_desc, n, ctx->d_fc_member, nm, nsig, ctx->d_fc_keys, key_cnt,
+                           expect ? ctx->d_fc_expect : NULL, ctx->d_fc_out, root ? ctx->d_fc_root : NULL, fec_block( big ), st ) ) ) return rc;
+    HIPCHK( hipMemcpyAsync( out + done, ctx->d_fc_out, n, hipMemcpyDeviceToHost, st ), -2 );
+    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, ctx->d_fc_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
+    int back = !d_arena && any_fill && nm;
+    if( back ) {
+      fl.resize( n );
+      HIPCHK( hipMemcpyAsync( fl.data(), ctx->d_fc_flag, n, hipMemcpyDeviceToHost, st ), -2 );
+      HIPCHK( hipMemcpyAsync( sl.h_payload, sl.d_payload, dsz, hipMemcpyDeviceToHost, st ), -2 );
+    }
+    if( stream_wait( ctx, st, 1 ) ) return -2;
+    if( back ) {
+      /* the proofs the GPU wrote into the staged shreds of sets that passed, to where the shreds came from */
+      for( unsigned long s=0UL; s<n; s++ ) {
+        if( fl[s] || td[s].member0 == 0xFFFFFFFFU ) continue;
+        unsigned long D = fd_fec_depth( td[s].cnt );
+        for( unsigned long j=0UL; j<td[s].cnt; j++ ) {
+          unsigned long k = (unsigned long)td[s].member0 + j;
+          if( !( tm[k].flags & FD_FEC_FILL ) ) continue;
+          unsigned char const * b = sl.h_payload + FD_SHRED_STRIDE * k;
+          unsigned int w[ FD_SHRED_FIELD_WORDS ];
+          memcpy( w, b + 64, sizeof(w) );
+          fd_shred_fields_t f; fd_shred_info_t in;
+          fd_shred_fields( w, &f );
+          if( fd_shred_classify( &f, FD_SHRED_CODE_SZ, FD_SHRED_STRICT_LEAF, &in ) ) continue;   /* (a set that passed: it classifies) */
+          memcpy( arena + from[k] + in.moff, b + in.moff, FD_SHRED_NODE_SZ * D );
+        }
+      }
+    }
     done += n;
   }
   return 0;

@@ -47,6 +47,16 @@ FDGPU_ERR_SHRED_PARSE = -19
 FDGPU_ERR_SHRED_MERKLE = -20
 FDGPU_SHRED_NO_SIG = 0xFFFF
 FDGPU_SHRED_STRICT_LEAF = 1
+FEC_DESC_DTYPE = np.dtype([("member0", "<u4"), ("cnt", "<u2"), ("key_idx", "<u2"), ("sig_idx", "<u4"), ("flags", "<u4")])
+FEC_MEMBER_DTYPE = np.dtype([("off", "<u4"), ("flags", "<u4")])
+assert FEC_DESC_DTYPE.itemsize == 16 and FEC_MEMBER_DTYPE.itemsize == 8
+FDGPU_ERR_FEC_MEMBER = -21
+FDGPU_ERR_FEC_ROOT = -22
+FDGPU_ERR_FEC_PROOF = -23
+FDGPU_FEC_LEAF_MAX = 256
+FDGPU_FEC_FILL = 1
+FDGPU_FEC_CHECK_ROOT = 1
+FDGPU_FEC_CHECK_PROOFS = 2
 ARENA_SLACK = 512            # readable bytes every device arena has behind its last byte
 TXN_IMG_STRIDE = 864
 
@@ -68,6 +78,7 @@ EXPORTS = ("fd_ed25519_verify", "fd_ed25519_verify_batch_single_msg", "fd_ed2551
            "fdgpu_ed25519_submit_raw_gather_to", "fdgpu_ed25519_set_dedup_seeds", "fdgpu_ed25519_debug_fail_launch",
            "fdgpu_ed25519_sigs_prepare", "fdgpu_ed25519_verify_sigs_device", "fdgpu_ed25519_verify_sigs_host",
            "fdgpu_ed25519_shreds_prepare", "fdgpu_ed25519_verify_shreds_device", "fdgpu_ed25519_verify_shreds_host",
+           "fdgpu_ed25519_fec_prepare", "fdgpu_ed25519_verify_fec_sets_device", "fdgpu_ed25519_verify_fec_sets_host",
            "fdgpu_sha256_batch_device", "fdgpu_sha256_batch_host",
            "fdgpu_last_error")
 
@@ -177,6 +188,17 @@ def load_library():
         L.fdgpu_ed25519_verify_shreds_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
                                                       ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
                                                       ctypes.c_void_p]
+        L.fdgpu_ed25519_fec_prepare.restype = ctypes.c_int
+        L.fdgpu_ed25519_fec_prepare.argtypes = [ctypes.c_void_p, ctypes.c_ulong, ctypes.c_ulong, ctypes.c_ulong]
+        L.fdgpu_ed25519_verify_fec_sets_device.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_fec_sets_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                          ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_ulong,
+                                                          ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p]
+        L.fdgpu_ed25519_verify_fec_sets_host.restype = ctypes.c_int
+        L.fdgpu_ed25519_verify_fec_sets_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                        ctypes.c_ulong, ctypes.c_void_p, ctypes.c_ulong, ctypes.c_void_p,
+                                                        ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_sha256_batch_device.restype = ctypes.c_int
         L.fdgpu_sha256_batch_device.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_ulong, ctypes.c_void_p, ctypes.c_void_p]
         L.fdgpu_sha256_batch_host.restype = ctypes.c_int
@@ -564,6 +586,57 @@ class Engine:
                                                        d_out, d_root, stream)
         if rc:
             raise RuntimeError(f"fdgpu_ed25519_verify_shreds_device: {rc} {last_error()}", rc)
+
+    # -- FEC sets: the whole tree, root, proofs and verdict -----------------------
+    def fec_prepare(self, max_sets: int, max_members: int, max_keys: int = 1) -> None:
+        """fdgpu_ed25519_fec_prepare: the device buffers of verify_fec_sets_device and verify_fec_sets_host.  Raises
+        on a refusal, with the C return value as the exception's second argument."""
+        rc = self.L.fdgpu_ed25519_fec_prepare(self.ctx, max_sets, max_members, max_keys)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_fec_prepare: {rc} {last_error()}", rc)
+
+    def verify_fec_sets_host(self, arena: np.ndarray, desc: np.ndarray, member: np.ndarray, keys=b"", expect=None,
+                             arena_sz: int | None = None, want_root: bool = True):
+        """(codes, roots) of the FEC sets that desc (FEC_DESC_DTYPE) and member (FEC_MEMBER_DTYPE) name inside the
+        first arena_sz bytes of arena, a uint8 array, which is updated in place: the proofs of FDGPU_FEC_FILL members
+        of sets that passed.  The code is FDGPU_ERR_DESC / FDGPU_ERR_FEC_MEMBER / FDGPU_ERR_FEC_ROOT /
+        FDGPU_ERR_FEC_PROOF, else 0 for a set whose key_idx is FDGPU_SHRED_NO_SIG, else fd_ed25519_verify of the root
+        under key key_idx of keys (32 bytes each).  expect: (n, 32) uint8 or None.  roots is (n, 32) uint8, or None
+        with want_root = False.  Synchronous; in place if the arena lies in a registered region (host_register).
+        Raises on a refusal, with the C return value as the exception's second argument."""
+        if arena_sz is None:
+            arena_sz = arena.nbytes - ARENA_SLACK
+        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and arena.flags.writeable and 0 <= arena_sz <= arena.nbytes
+        desc = np.ascontiguousarray(desc, dtype=FEC_DESC_DTYPE)
+        member = np.ascontiguousarray(member, dtype=FEC_MEMBER_DTYPE)
+        k = np.frombuffer(bytes(keys) + b"\0", np.uint8) if not isinstance(keys, np.ndarray) else \
+            np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        key_cnt = (len(k) - (0 if isinstance(keys, np.ndarray) else 1)) // 32
+        if expect is not None:
+            expect = np.ascontiguousarray(expect, np.uint8).reshape(-1)
+            assert len(expect) == 32 * len(desc)
+        out = np.zeros(max(len(desc), 1), np.int8)
+        root = np.zeros((max(len(desc), 1), 32), np.uint8) if want_root else None
+        rc = self.L.fdgpu_ed25519_verify_fec_sets_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
+                                                       member.ctypes.data if len(member) else None, len(member),
+                                                       k.ctypes.data, key_cnt,
+                                                       expect.ctypes.data if expect is not None and len(expect) else None,
+                                                       out.ctypes.data, root.ctypes.data if want_root else None)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_fec_sets_host: {rc} {last_error()}", rc)
+        return out[:len(desc)], (root[:len(desc)] if want_root else None)
+
+    def verify_fec_sets_device(self, d_arena: int, arena_sz: int, d_desc: int, set_cnt: int, d_member: int, member_cnt: int,
+                               sig_cnt: int, d_keys: int, key_cnt: int, d_expect: int | None, d_out: int,
+                               d_root: int | None = None, stream: int | None = None) -> None:
+        """Enqueue a batch of FEC sets resident in device memory (raw device pointers; d_arena, which is written, has
+        ARENA_SLACK readable bytes behind arena_sz; d_keys, d_expect and d_root are 16-byte aligned, the last two may
+        be None).  The caller numbers the keyed sets, sig_idx in [0, sig_cnt).  Raises on a refusal, with the C
+        return value as the second argument."""
+        rc = self.L.fdgpu_ed25519_verify_fec_sets_device(self.ctx, d_arena, arena_sz, d_desc, set_cnt, d_member, member_cnt,
+                                                         sig_cnt, d_keys, key_cnt, d_expect, d_out, d_root, stream)
+        if rc:
+            raise RuntimeError(f"fdgpu_ed25519_verify_fec_sets_device: {rc} {last_error()}", rc)
 
     # -- raw payloads: device fd_txn_parse + verify ---------------------------
     def verify_raw_host(self, payload: np.ndarray, off: np.ndarray, sz: np.ndarray, want_img: bool = False):

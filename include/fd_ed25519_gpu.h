@@ -464,6 +464,138 @@ fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t *      ctx,
                                   signed char *              out,
                                   unsigned char *            root );
 
+/* FEC sets: a complete set's whole Merkle tree -- the leaves of
+   its n shreds, the tree over them, the root, and a proof for every leaf --
+   where the shreds calls above walk one carried proof per shred.  Two
+   callers need it: the resolver when a set completes (src/disco/shred/
+   fd_fec_resolver.c:573-705: recovered shreds carry no proof yet, the whole
+   tree must agree with the signed root, the proofs are written into the
+   recovered shreds) and the leader's shredder (src/disco/shred/
+   fd_shredder.c:261-305: leaves, tree, root to sign, one proof per shred).
+   Reed-Solomon and signing stay on the host.
+
+   The tree (src/ballet/bmtree/fd_bmtree.c): a leaf is SHA-256( 0x00
+   "SOLANA_MERKLE_SHREDS_LEAF" shred[64, moff) ); node j of layer l + 1 is
+   SHA-256( 0x01 "SOLANA_MERKLE_SHREDS_NODE" a[0,20) b[0,20) ) of layer l's
+   nodes a = 2j and b = 2j + 1, the last node of an odd layer merged with
+   itself; D = 0 for n = 1, else floor( log2( n - 1 ) ) + 1; the root is the
+   one node of layer D (all 32 bytes; for n = 1 the leaf); leaf j's proof
+   node at layer l is the first 20 bytes of node ( j >> l ) ^ 1, or of node
+   j >> l where that index is past the layer's end.
+
+   Set i's leaves are members [member0, member0 + cnt) of the member array
+   in tree order; member j's shred lies at arena + off (any alignment).
+   out[i] is the first of these that applies (firedancer_amd/csrc/
+   fd_fec_desc.h has the rules as code):
+     FDGPU_ERR_DESC        cnt is 0 or above 256; member0 + cnt > member_cnt
+                           (64 bits); the key or the slot is bad as for
+                           shreds; a member has off + 1203 > arena_sz, or is
+                           a code shred with off + 1228 > arena_sz (the
+                           variant byte is read only once off + 1203 <=
+                           arena_sz holds);
+     FDGPU_ERR_FEC_MEMBER  for some member j: fd_shred_parse fails on its
+                           1203 (data) or 1228 (code) bytes or it is legacy,
+                           its proof depth is not D, its leaf index is not
+                           j; slot, version or fec_set_idx differ from member
+                           0's; its type is neither member 0's nor that
+                           type's mate of the other kind; a data member's
+                           parent_off differs from member 0's; a code
+                           member's data_cnt + code_cnt is not cnt, or either
+                           differs from the first code member's; a chained
+                           member's chained root differs from member 0's; its
+                           signature differs from member 0's;
+     FDGPU_ERR_FEC_ROOT    FDGPU_FEC_CHECK_ROOT and the root is not
+                           expect[32 i, 32 i + 32) (or there is no expect);
+     FDGPU_ERR_FEC_PROOF   FDGPU_FEC_CHECK_PROOFS and a member without
+                           FDGPU_FEC_FILL carries other proof bytes than the
+                           tree's;
+   else FD_ED25519_SUCCESS without a key, else fd_ed25519_verify( root, 32,
+   member 0's signature, keys + 32 key_idx ) under the context's semantics,
+   through signature slots as for shreds.  root[32 i, 32 i + 32) gets the
+   root, or zeros under the first two codes.  The proofs of FILL members are
+   written into their shreds exactly when none of the four codes applies,
+   whatever the signature's code; nothing else in the arena changes, and a
+   bad set changes no other set's result.  A member named by two sets with
+   FILL is the caller's error and harms nothing else. */
+#define FDGPU_ERR_FEC_MEMBER   (-21)
+#define FDGPU_ERR_FEC_ROOT     (-22)
+#define FDGPU_ERR_FEC_PROOF    (-23)
+#define FDGPU_FEC_LEAF_MAX     (256u)      /* fd_shred_parse: data_cnt + code_cnt <= 256 */
+#define FDGPU_FEC_FILL         (1u)        /* member flags: write this shred's proof */
+#define FDGPU_FEC_CHECK_ROOT   (1u)        /* set flags: root must equal expect[32 i, +32) */
+#define FDGPU_FEC_CHECK_PROOFS (2u)        /* set flags: every non-FILL member's carried proof must equal the tree's */
+
+typedef struct fdgpu_fec_member { unsigned int off; unsigned int flags; } fdgpu_fec_member_t;   /* 8 bytes */
+typedef struct fdgpu_fec_desc {             /* 16 bytes */
+  unsigned int   member0;  /* index of the set's leaf 0 in the member array; leaves are members
+                              [member0, member0 + cnt) in tree order */
+  unsigned short cnt;      /* leaves, 1..256 */
+  unsigned short key_idx;  /* leader key, or FDGPU_SHRED_NO_SIG */
+  unsigned int   sig_idx;  /* as fdgpu_shred_desc_t.sig_idx */
+  unsigned int   flags;
+} fdgpu_fec_desc_t;
+
+/* fdgpu_ed25519_fec_prepare: the device memory of the two calls below, for
+   batches of at most max_sets sets, max_members members and max_keys keys
+   (<= 65,535); signature slots for min( max_sig, max_txn, max_sets, 2^24 )
+   sets.  As fdgpu_ed25519_shreds_prepare: it waits for the device, only
+   grows, and returns 0, -1 bad arguments, -2 the allocation failed (the
+   context is then unprepared), -3 faulted. */
+int
+fdgpu_ed25519_fec_prepare( fdgpu_ed25519_ctx_t * ctx,
+                           unsigned long         max_sets,
+                           unsigned long         max_members,
+                           unsigned long         max_keys );
+
+/* Device form.  d_arena (512 readable bytes after arena_sz) is written: the
+   proofs of FILL members.  d_desc, d_member, d_keys, d_expect (32 set_cnt
+   bytes, or NULL), d_out (set_cnt codes) and d_root (32 set_cnt bytes, or
+   NULL) are device memory; d_keys, d_expect and d_root are 16-byte aligned.
+   Asynchronous on `stream` (NULL = the ctx's own), one batch of the context
+   at a time.  -1 (nothing launched) if a count exceeds what was prepared;
+   -3 on a faulted or unprepared context. */
+int
+fdgpu_ed25519_verify_fec_sets_device( fdgpu_ed25519_ctx_t *      ctx,
+                                      unsigned char *            d_arena,
+                                      unsigned long              arena_sz,
+                                      fdgpu_fec_desc_t const *   d_desc,
+                                      unsigned long              set_cnt,
+                                      fdgpu_fec_member_t const * d_member,
+                                      unsigned long              member_cnt,
+                                      unsigned long              sig_cnt,
+                                      unsigned char const *      d_keys,
+                                      unsigned long              key_cnt,
+                                      unsigned char const *      d_expect,
+                                      signed char *              d_out,
+                                      unsigned char *            d_root,
+                                      void *                     stream );
+
+/* Host form.  Synchronous; -1 while the async pipeline holds anything.
+   sig_idx is computed here, and the sets go in chunks of whole sets within
+   the prepared counts.  If [arena, arena + arena_sz + 512) lies inside one
+   registered region the GPU works in place; otherwise each member's shred
+   goes through the staging slot at a 1,232-byte stride with rewritten
+   members, and afterwards the 20 D proof bytes of every FILL member of a set
+   that passed are copied back into arena.  Both branches give identical
+   codes, roots and arena bytes.  expect and root may be NULL; -1 if a set has
+   FDGPU_FEC_CHECK_ROOT and expect is NULL, if key_cnt exceeds max_keys, or
+   if one set holds more members than a batch may (max_members, and on the
+   staged branch what the staging slot holds); -3 on a faulted or unprepared
+   context. */
+int
+fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t *      ctx,
+                                    unsigned char *            arena,
+                                    unsigned long              arena_sz,
+                                    fdgpu_fec_desc_t const *   desc,
+                                    unsigned long              set_cnt,
+                                    fdgpu_fec_member_t const * member,
+                                    unsigned long              member_cnt,
+                                    unsigned char const *      keys,
+                                    unsigned long              key_cnt,
+                                    unsigned char const *      expect,
+                                    signed char *              out,
+                                    unsigned char *            root );
+
 /* Batch SHA-256, the sibling of the SHA-512 calls below: hash[32 t, 32 t +
    32) = SHA-256 of the sz[t] < 2^29 bytes at data + off[t] (any alignment).
    The device form reads up to 67 bytes past each message, so d_data must
