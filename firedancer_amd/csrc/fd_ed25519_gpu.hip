@@ -3862,6 +3862,21 @@ struct fd_slot {               /* one in-flight host batch of the async pipeline
 #define FD_NRING 64    /* batches whose kernel boundaries are kept while timing is on */
 #define FD_NGT   64    /* gathers timed at once */
 
+/* A slot front-end (Merkle shreds, FEC sets): the device memory a context owns to derive a 32-byte root per record and
+   have the verify batch check the signatures over the roots of the keyed ones (front_prepare) */
+struct fd_front {
+  unsigned long       max;       /*   records a batch may hold; 0 = unprepared */
+  unsigned long       keys;      /*   keys a batch may name */
+  unsigned long       sig;       /*   signature slots: min( max_sig, max_txn, max ) */
+  unsigned char *     d_pack;    /*   [128 sig + 2 FD_ARENA_SLACK] the slots, sig | key | root */
+  fdgpu_txn_desc_t *  d_tdesc;   /*   [sig] the slots as one-signer transactions */
+  i8 *                d_code;    /*   [sig] the batch's code of each slot */
+  i8 *                d_flag;    /*   [max] a record's own code, 0 = none */
+  i8 *                d_out;     /*   [max] the host form's codes */
+  unsigned char *     d_root;    /*   [32 max] the host form's roots */
+  unsigned char *     d_keys;    /*   [32 keys] the host form's keys */
+};
+
 struct fdgpu_ed25519_ctx {
   int device, semantics, timing;
   std::vector<void *> dev_mem, pin_mem;   /* every device / pinned buffer of the context and its slots (ctx_dev_alloc,
@@ -3973,34 +3988,16 @@ struct fdgpu_ed25519_ctx {
   unsigned char *     d_sg_flag; /*   [max_sig] FD_SIG_DESC_BAD | FD_SIG_DESC_OVER */
   i8 *                d_sg_out;  /*   [max_sig] the host form's codes */
   unsigned long *     d_sg_btot; /*   [max_sig / FD_WG + 1] the blocks' totals, then their prefix sum */
-  /* Merkle shreds (fdgpu_ed25519_shreds_prepare): all device memory */
-  unsigned long       sh_max;    /*   records a batch may hold; 0 = unprepared */
-  unsigned long       sh_keys;   /*   keys a batch may name */
-  unsigned long       sh_sig;    /*   signature slots: min( max_sig, max_txn, sh_max ) */
-  unsigned char *     d_sh_pack; /*   [128 sh_sig + 2 FD_ARENA_SLACK] the slots, sig | key | root */
-  fdgpu_txn_desc_t *  d_sh_tdesc;/*   [sh_sig] the slots as one-signer transactions */
-  i8 *                d_sh_code; /*   [sh_sig] the batch's code of each slot */
-  i8 *                d_sh_flag; /*   [sh_max] a record's flagged code, 0 = none */
-  fdgpu_shred_desc_t * d_sh_desc;/*   [sh_max] the host form's uploaded descriptors */
-  i8 *                d_sh_out;  /*   [sh_max] the host form's codes */
-  unsigned char *     d_sh_root; /*   [32 sh_max] the host form's roots */
-  unsigned char *     d_sh_keys; /*   [32 sh_keys] the host form's keys */
-  /* FEC sets (fdgpu_ed25519_fec_prepare): all device memory */
-  unsigned long       fc_sets;   /*   sets a batch may hold; 0 = unprepared */
+  /* Merkle shreds (fdgpu_ed25519_shreds_prepare): a front-end whose records are shreds, and */
+  fd_front            sh;
+  fdgpu_shred_desc_t * d_sh_desc;/*   [sh.max] the host form's uploaded descriptors */
+  /* FEC sets (fdgpu_ed25519_fec_prepare): a front-end whose records are sets, and */
+  fd_front            fc;
   unsigned long       fc_members;/*   members a batch may hold */
-  unsigned long       fc_keys;   /*   keys a batch may name */
-  unsigned long       fc_sig;    /*   signature slots: min( max_sig, max_txn, fc_sets ) */
   unsigned long       fc_all;    /*   sets whose 256-lane blocks are all resident at once: 4 a CU (fd_fec_tree_kernel: 4 waves a SIMD) */
-  unsigned char *     d_fc_pack; /*   [128 fc_sig + 2 FD_ARENA_SLACK] the slots, sig | key | root */
-  fdgpu_txn_desc_t *  d_fc_tdesc;/*   [fc_sig] the slots as one-signer transactions */
-  i8 *                d_fc_code; /*   [fc_sig] the batch's code of each slot */
-  i8 *                d_fc_flag; /*   [fc_sets] a set's own code, 0 = none */
-  fdgpu_fec_desc_t *  d_fc_desc; /*   [fc_sets] the host form's uploaded descriptors */
+  fdgpu_fec_desc_t *  d_fc_desc; /*   [fc.max] the host form's uploaded descriptors */
   fdgpu_fec_member_t * d_fc_member; /* [fc_members] the host form's uploaded members */
-  i8 *                d_fc_out;  /*   [fc_sets] the host form's codes */
-  unsigned char *     d_fc_root; /*   [32 fc_sets] the host form's roots */
-  unsigned char *     d_fc_expect; /* [32 fc_sets] the host form's expected roots */
-  unsigned char *     d_fc_keys; /*   [32 fc_keys] the host form's keys */
+  unsigned char *     d_fc_expect; /* [32 fc.max] the host form's expected roots */
   hipEvent_t ev[5];
   hipEvent_t ring[ FD_NRING ][ 5 ];  /* per-batch kernel boundaries while timing is on: prep start, walk start, walk end,
                                      reduce end, and (throughput path) the decode kernel's end inside the prep */
@@ -4051,12 +4048,21 @@ struct fdgpu_ed25519_ctx {
 /* Context memory: every device buffer of a context and of its slots comes from ctx_dev_alloc and every pinned
    one from ctx_pin_alloc (which also gives its device view, if asked).  Both record the pointer, and
    fdgpu_ed25519_ctx_delete frees from those records: a new buffer is named once, where it is allocated.
+   ctx_dev_free gives one back before that (a prepare call that grows its buffers) and takes its record out.
    (d_khash lives inside verify_long only and is not recorded.) */
 template< class T > static hipError_t
 ctx_dev_alloc( fdgpu_ed25519_ctx_t * ctx, T ** p, size_t sz ) {
   hipError_t e = hipMalloc( (void **)p, sz );
   if( e == hipSuccess ) ctx->dev_mem.push_back( (void *)*p );
   return e;
+}
+template< class T > static void
+ctx_dev_free( fdgpu_ed25519_ctx_t * ctx, T ** p ) {
+  if( !*p ) return;
+  for( size_t i=0; i<ctx->dev_mem.size(); i++ )
+    if( ctx->dev_mem[i] == (void *)*p ) { ctx->dev_mem.erase( ctx->dev_mem.begin() + (long)i ); break; }
+  (void)hipFree( *p );
+  *p = NULL;
 }
 template< class T, class U = T > static hipError_t
 ctx_pin_alloc( fdgpu_ed25519_ctx_t * ctx, T ** p, size_t sz, U ** dev = NULL ) {
@@ -4957,6 +4963,21 @@ verify_chunks( fdgpu_ed25519_ctx_t * ctx, unsigned long cnt, signed char * out, 
   return 0;
 }
 
+/* A (msg, sig, pub) triple as a one-signer transaction: its descriptor, and its bytes sig | pub | msg */
+static fdgpu_txn_desc_t
+one_signer_desc( unsigned long msg_sz ) {
+  fdgpu_txn_desc_t d = {};
+  d.payload_sz = (unsigned short)( 96UL + msg_sz );
+  d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
+  return d;
+}
+static void
+pack_triple( unsigned char * dst, unsigned char const * sig, unsigned char const * pub, unsigned char const * msg,
+             unsigned long msg_sz ) {
+  memcpy( dst, sig, 64 ); memcpy( dst + 64, pub, 32 );
+  if( msg_sz ) memcpy( dst + 96, msg, msg_sz );
+}
+
 /* Independent (msg, sig, pub) triples -- the batched form of
    fd_ed25519_verify for callers that verify unrelated messages (gossip
    CRDS values and ping/pong, fd_gossvf_tile.c:367-446; precompiles).
@@ -4971,16 +4992,8 @@ fdgpu_ed25519_verify_many_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
   for( unsigned long i=0; i<cnt; i++ )
     if( msg_szs[i] > 0xffffUL - 96UL || 96UL + msg_szs[i] + 8UL > ctx->max_payload ) { fd_err = "message too long"; return -1; }
   return verify_chunks( ctx, cnt, out,
-    [&]( unsigned long i ) {
-      fdgpu_txn_desc_t d = {};
-      d.payload_sz = (unsigned short)( 96UL + msg_szs[i] );
-      d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
-      return d;
-    },
-    [&]( unsigned long i, unsigned char * b ) {
-      memcpy( b, sigs[i], 64 ); memcpy( b + 64, pubs[i], 32 );
-      if( msg_szs[i] ) memcpy( b + 96, msgs[i], msg_szs[i] );
-    } );
+    [&]( unsigned long i ) { return one_signer_desc( msg_szs[i] ); },
+    [&]( unsigned long i, unsigned char * b ) { pack_triple( b, sigs[i], pubs[i], msgs[i], msg_szs[i] ); } );
 }
 
 /* Transactions scattered in host memory, each already parsed (the replay
@@ -5007,10 +5020,17 @@ fdgpu_ed25519_verify_txn_ptrs( fdgpu_ed25519_ctx_t * ctx, unsigned char const * 
 
 /* ---- per-signature descriptors ------------------------------ */
 
+/* What every entry point of the descriptor front-ends refuses first, like HIPCHK by returning: no
+   context, then a faulted one; and, where the call needs it, a context that `prepare` has not prepared (cap: the
+   prepared size, 0 = none).  Behind them a call checks its sizes, returns 0 for no records, refuses a NULL and then
+   a misaligned argument, in this order. */
+#define FRONT_CTX( ctx ) do { if( !(ctx) ) { fd_err = "NULL ctx"; return -1; }                                           \
+    if( (ctx)->fault ) { fd_err = std::string( __func__ ) + ": the context has faulted"; return -3; } } while(0)
+#define FRONT_PREPARED( cap, prepare ) do { if( !(cap) ) { fd_err = std::string( __func__ ) + ": no " prepare; return -3; } } while(0)
+
 extern "C" int
 fdgpu_ed25519_sigs_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_packed_bytes ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_sigs_prepare: the context has faulted"; return -3; }
+  FRONT_CTX( ctx );
   if( max_packed_bytes < FD_SIG_DESC_HDR || max_packed_bytes + FD_ARENA_SLACK > ( 1UL << 32 ) ) {
     fd_err = "fdgpu_ed25519_sigs_prepare: bad size"; return -1;
   }
@@ -5027,12 +5047,8 @@ fdgpu_ed25519_sigs_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_packed_
   if( max_packed_bytes <= ctx->sg_cap ) return 0;
   /* a larger arena: nothing of the context may still read the old one */
   HIPCHK( hipDeviceSynchronize(), -2 );
-  if( ctx->d_sg_pack ) {
-    for( size_t i=0; i<ctx->dev_mem.size(); i++ )
-      if( ctx->dev_mem[i] == (void *)ctx->d_sg_pack ) { ctx->dev_mem.erase( ctx->dev_mem.begin() + (long)i ); break; }
-    (void)hipFree( ctx->d_sg_pack );
-    ctx->d_sg_pack = NULL; ctx->sg_cap = 0UL;
-  }
+  ctx->sg_cap = 0UL;
+  ctx_dev_free( ctx, &ctx->d_sg_pack );
   size_t bytes = max_packed_bytes + 2UL * FD_ARENA_SLACK;
   HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sg_pack, bytes ), -2 );
   HIPCHK( hipMemsetAsync( ctx->d_sg_pack, 0, bytes, ctx->stream ), -2 );
@@ -5067,9 +5083,7 @@ extern "C" int
 fdgpu_ed25519_verify_sigs_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
                                   fdgpu_sig_desc_t const * d_desc, unsigned long cnt, unsigned long msg_bytes,
                                   signed char * d_out, void * stream ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_sigs_device: the context has faulted"; return -3; }
-  if( !ctx->sg_cap ) { fd_err = "fdgpu_ed25519_verify_sigs_device: no fdgpu_ed25519_sigs_prepare"; return -3; }
+  FRONT_CTX( ctx ); FRONT_PREPARED( ctx->sg_cap, "fdgpu_ed25519_sigs_prepare" );
   if( cnt > ctx->max_sig || cnt > ctx->max_txn ) { fd_err = "batch larger than ctx"; return -1; }
   if( msg_bytes > ctx->sg_cap || 104UL * cnt > ctx->sg_cap - msg_bytes ) {
     fd_err = "fdgpu_ed25519_verify_sigs_device: 104 cnt + msg_bytes exceeds the prepared size"; return -1;
@@ -5083,15 +5097,14 @@ fdgpu_ed25519_verify_sigs_device( fdgpu_ed25519_ctx_t * ctx, unsigned char const
 extern "C" int
 fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * arena, unsigned long arena_sz,
                                 fdgpu_sig_desc_t const * desc, unsigned long cnt, signed char * out ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_sigs_host: the context has faulted"; return -3; }
+  FRONT_CTX( ctx );
   if( !cnt ) return 0;
   if( !arena || !desc || !out ) { fd_err = "NULL argument"; return -1; }
   int rc;
   unsigned char const * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
   if( d_arena ) {
     /* in place: the GPU packs each chunk straight from the caller's region */
-    if( !ctx->sg_cap ) { fd_err = "fdgpu_ed25519_verify_sigs_host: no fdgpu_ed25519_sigs_prepare"; return -3; }
+    FRONT_PREPARED( ctx->sg_cap, "fdgpu_ed25519_sigs_prepare" );
     if( ( rc = sync_begin( ctx ) ) ) return rc;
     hipStream_t st = ctx->stream;
     unsigned long most = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
@@ -5128,16 +5141,8 @@ fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
     unsigned long m = 1UL;
     while( i + m < cnt && !fd_sig_desc_bad( r[m].sig_off, r[m].pub_off, r[m].msg_off, r[m].msg_sz, arena_sz ) ) m++;
     rc = verify_chunks( ctx, m, out + i,
-      [&]( unsigned long k ) {
-        fdgpu_txn_desc_t d = {};
-        d.payload_sz = (unsigned short)( 96U + r[k].msg_sz );
-        d.message_off = 96; d.acct_addr_off = 64; d.signature_off = 0; d.sig_cnt = 1;
-        return d;
-      },
-      [&]( unsigned long k, unsigned char * b ) {
-        memcpy( b, arena + r[k].sig_off, 64 ); memcpy( b + 64, arena + r[k].pub_off, 32 );
-        if( r[k].msg_sz ) memcpy( b + 96, arena + r[k].msg_off, r[k].msg_sz );
-      } );
+      [&]( unsigned long k ) { return one_signer_desc( r[k].msg_sz ); },
+      [&]( unsigned long k, unsigned char * b ) { pack_triple( b, arena + r[k].sig_off, arena + r[k].pub_off, arena + r[k].msg_off, r[k].msg_sz ); } );
     if( rc ) return rc;
     i += m;
   }
@@ -5148,48 +5153,84 @@ fdgpu_ed25519_verify_sigs_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const *
 
 #define FD_SHRED_STRIDE 1232UL     /* the host form's staging: a shred's first min( sz, 1228 ) bytes every 1,232 */
 
-template< class T > static void
-ctx_dev_free( fdgpu_ed25519_ctx_t * ctx, T ** p ) {
-  if( !*p ) return;
-  for( size_t i=0; i<ctx->dev_mem.size(); i++ )
-    if( ctx->dev_mem[i] == (void *)*p ) { ctx->dev_mem.erase( ctx->dev_mem.begin() + (long)i ); break; }
-  (void)hipFree( *p );
-  *p = NULL;
+/* A front-end's device buffers grow in two steps, the caller's own buffers between them.  front_release: larger
+   buffers, so nothing of the context may still read the old ones; unprepared, then they go.  front_prepare: buffers
+   for records and keys, the pack zeroed, and only then prepared. */
+static int
+front_release( fdgpu_ed25519_ctx_t * ctx, fd_front * f ) {
+  HIPCHK( hipDeviceSynchronize(), -2 );
+  f->max = 0UL; f->keys = 0UL; f->sig = 0UL;
+  ctx_dev_free( ctx, &f->d_pack ); ctx_dev_free( ctx, &f->d_tdesc ); ctx_dev_free( ctx, &f->d_code );
+  ctx_dev_free( ctx, &f->d_flag ); ctx_dev_free( ctx, &f->d_out );   ctx_dev_free( ctx, &f->d_root );
+  ctx_dev_free( ctx, &f->d_keys );
+  return 0;
+}
+static int
+front_prepare( fdgpu_ed25519_ctx_t * ctx, fd_front * f, unsigned long records, unsigned long keys ) {
+  size_t ns = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
+  if( ns > records ) ns = records;
+  if( ns > ( 1UL << 24 ) ) ns = 1UL << 24;                   /* (128 ns + slack inside payload_off's 32 bits) */
+  size_t pack = FD_SHRED_SLOT * ns + 2UL * FD_ARENA_SLACK;
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_pack, pack ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_code, ns ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_flag, records ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_out, records ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_root, 32UL * records ), -2 );
+  HIPCHK( ctx_dev_alloc( ctx, &f->d_keys, 32UL * keys ), -2 );
+  HIPCHK( hipMemsetAsync( f->d_pack, 0, pack, ctx->stream ), -2 );
+  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
+  f->max = records; f->keys = keys; f->sig = ns;
+  return 0;
+}
+
+/* the head and the tail that the front-ends' batches share: the slots, and the verify batch over them */
+static void
+front_slots( fd_front const & f, unsigned long sig_cnt, hipStream_t st ) {
+  if( sig_cnt )
+    hipLaunchKernelGGL( fd_shred_slot_kernel, dim3( (unsigned)( ( sig_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
+                        (uint4 *)f.d_pack, f.d_tdesc, (u32)sig_cnt );
+}
+static int
+front_verify( fdgpu_ed25519_ctx_t * ctx, fd_front const & f, unsigned long sig_cnt, hipStream_t st ) {
+  if( !sig_cnt ) { ctx->last_path = FDGPU_PATH_NONE; return 0; }   /* a batch without signatures */
+  return launch_batch( ctx, f.d_pack, f.d_tdesc, sig_cnt, sig_cnt, f.d_code, NULL, st );
+}
+
+/* What the two host forms share.  front_arena: the arena's device address if it lies, slack included, in a
+   registered region; else NULL: any other host memory, the shreds go through the staging slot, one every
+   FD_SHRED_STRIDE bytes, and *most comes down to those the slot holds.  front_stage: a chunk of n staged shreds,
+   zero slack behind them, up to the slot's device arena, which *da and *dsz then name. */
+static int
+front_arena( fdgpu_ed25519_ctx_t const * ctx, unsigned char const * arena, unsigned long arena_sz, unsigned char ** d_arena,
+             unsigned long * most ) {
+  if( ( *d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK ) ) ) return 0;
+  if( *most > ctx->max_payload / FD_SHRED_STRIDE ) *most = ctx->max_payload / FD_SHRED_STRIDE;
+  return sync_ctx( ctx, 1 );
+}
+static int
+front_stage( fd_slot & sl, unsigned long n, unsigned char ** da, unsigned long * dsz, hipStream_t st ) {
+  *dsz = FD_SHRED_STRIDE * n;
+  memset( sl.h_payload + *dsz, 0, FD_ARENA_SLACK );
+  HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, *dsz + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
+  *da = sl.d_payload;
+  return 0;
 }
 
 extern "C" int
 fdgpu_ed25519_shreds_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_shreds, unsigned long max_keys ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_shreds_prepare: the context has faulted"; return -3; }
+  FRONT_CTX( ctx );
   if( !max_shreds || max_shreds >= ( 1UL << 31 ) || !max_keys || max_keys > (unsigned long)FD_SHRED_NO_SIG ) {
     fd_err = "fdgpu_ed25519_shreds_prepare: bad size"; return -1;
   }
-  if( max_shreds <= ctx->sh_max && max_keys <= ctx->sh_keys ) return 0;
+  if( max_shreds <= ctx->sh.max && max_keys <= ctx->sh.keys ) return 0;
   HIPCHK( hipSetDevice( ctx->device ), -2 );
-  if( max_shreds < ctx->sh_max  ) max_shreds = ctx->sh_max;
-  if( max_keys   < ctx->sh_keys ) max_keys   = ctx->sh_keys;
-  /* larger buffers: nothing of the context may still read the old ones */
-  HIPCHK( hipDeviceSynchronize(), -2 );
-  ctx->sh_max = 0UL; ctx->sh_keys = 0UL; ctx->sh_sig = 0UL;
-  ctx_dev_free( ctx, &ctx->d_sh_pack ); ctx_dev_free( ctx, &ctx->d_sh_tdesc ); ctx_dev_free( ctx, &ctx->d_sh_code );
-  ctx_dev_free( ctx, &ctx->d_sh_flag ); ctx_dev_free( ctx, &ctx->d_sh_desc );  ctx_dev_free( ctx, &ctx->d_sh_out );
-  ctx_dev_free( ctx, &ctx->d_sh_root ); ctx_dev_free( ctx, &ctx->d_sh_keys );
-  size_t ns = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
-  if( ns > max_shreds ) ns = max_shreds;
-  if( ns > ( 1UL << 24 ) ) ns = 1UL << 24;                   /* (128 ns + slack inside payload_off's 32 bits) */
-  size_t pack = FD_SHRED_SLOT * ns + 2UL * FD_ARENA_SLACK;
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_pack, pack ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_code, ns ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_flag, max_shreds ), -2 );
+  if( max_shreds < ctx->sh.max  ) max_shreds = ctx->sh.max;
+  if( max_keys   < ctx->sh.keys ) max_keys   = ctx->sh.keys;
+  if( front_release( ctx, &ctx->sh ) ) return -2;
+  ctx_dev_free( ctx, &ctx->d_sh_desc );
   HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_desc, max_shreds * sizeof(fdgpu_shred_desc_t) ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_out, max_shreds ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_root, 32UL * max_shreds ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_sh_keys, 32UL * max_keys ), -2 );
-  HIPCHK( hipMemsetAsync( ctx->d_sh_pack, 0, pack, ctx->stream ), -2 );
-  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
-  ctx->sh_max = max_shreds; ctx->sh_keys = max_keys; ctx->sh_sig = ns;
-  return 0;
+  return front_prepare( ctx, &ctx->sh, max_shreds, max_keys );
 }
 
 /* the kernels of one batch of shreds on st: the slots, the roots, the batch over the slots, the codes */
@@ -5197,20 +5238,16 @@ static int
 shreds_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char const * d_arena, unsigned long arena_sz,
                fdgpu_shred_desc_t const * d_desc, unsigned long cnt, unsigned long sig_cnt, unsigned char const * d_keys,
                unsigned long key_cnt, i8 * d_out, unsigned char * d_root, hipStream_t st ) {
+  fd_front const & f = ctx->sh;
   unsigned nb = (unsigned)( ( cnt + FD_WG - 1 ) / FD_WG );
-  if( sig_cnt )
-    hipLaunchKernelGGL( fd_shred_slot_kernel, dim3( (unsigned)( ( sig_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
-                        (uint4 *)ctx->d_sh_pack, ctx->d_sh_tdesc, (u32)sig_cnt );
+  front_slots( f, sig_cnt, st );
   hipLaunchKernelGGL( fd_shred_root_kernel, dim3(nb), dim3(FD_WG), 0, st, d_arena, arena_sz, d_desc, (u32)cnt, (u32)sig_cnt,
-                      (uint4 const *)d_keys, (u32)key_cnt, (uint4 *)ctx->d_sh_pack, ctx->d_sh_tdesc, ctx->d_sh_flag,
-                      (uint4 *)d_root );
+                      (uint4 const *)d_keys, (u32)key_cnt, (uint4 *)f.d_pack, f.d_tdesc, f.d_flag, (uint4 *)d_root );
   HIPCHK( hipGetLastError(), -3 );
-  if( sig_cnt ) {
-    int rc = launch_batch( ctx, ctx->d_sh_pack, ctx->d_sh_tdesc, sig_cnt, sig_cnt, ctx->d_sh_code, NULL, st );
-    if( rc ) return rc;
-  } else ctx->last_path = FDGPU_PATH_NONE;                    /* a batch without signatures */
-  hipLaunchKernelGGL( fd_shred_flag_kernel, dim3(nb), dim3(FD_WG), 0, st, d_desc, (u32)cnt, (i8 const *)ctx->d_sh_flag,
-                      (i8 const *)ctx->d_sh_code, d_out );
+  int rc = front_verify( ctx, f, sig_cnt, st );
+  if( rc ) return rc;
+  hipLaunchKernelGGL( fd_shred_flag_kernel, dim3(nb), dim3(FD_WG), 0, st, d_desc, (u32)cnt, (i8 const *)f.d_flag,
+                      (i8 const *)f.d_code, d_out );
   HIPCHK( hipGetLastError(), -3 );
   return 0;
 }
@@ -5220,10 +5257,8 @@ fdgpu_ed25519_verify_shreds_device( fdgpu_ed25519_ctx_t * ctx, unsigned char con
                                     fdgpu_shred_desc_t const * d_desc, unsigned long cnt, unsigned long sig_cnt,
                                     unsigned char const * d_keys, unsigned long key_cnt, signed char * d_out,
                                     unsigned char * d_root, void * stream ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_shreds_device: the context has faulted"; return -3; }
-  if( !ctx->sh_max ) { fd_err = "fdgpu_ed25519_verify_shreds_device: no fdgpu_ed25519_shreds_prepare"; return -3; }
-  if( cnt > ctx->sh_max || sig_cnt > ctx->sh_sig || key_cnt > ctx->sh_keys ) { fd_err = "batch larger than prepared"; return -1; }
+  FRONT_CTX( ctx ); FRONT_PREPARED( ctx->sh.max, "fdgpu_ed25519_shreds_prepare" );
+  if( cnt > ctx->sh.max || sig_cnt > ctx->sh.sig || key_cnt > ctx->sh.keys ) { fd_err = "batch larger than prepared"; return -1; }
   if( !cnt ) return 0;
   if( !d_arena || !d_desc || !d_out || ( key_cnt && !d_keys ) ) { fd_err = "NULL argument"; return -1; }
   if( ( (uintptr_t)d_keys | (uintptr_t)d_root ) & 15UL ) { fd_err = "d_keys and d_root are 16-byte aligned"; return -1; }
@@ -5236,26 +5271,20 @@ extern "C" int
 fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const * arena, unsigned long arena_sz,
                                   fdgpu_shred_desc_t const * desc, unsigned long cnt, unsigned char const * keys,
                                   unsigned long key_cnt, signed char * out, unsigned char * root ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_shreds_host: the context has faulted"; return -3; }
-  if( !ctx->sh_max ) { fd_err = "fdgpu_ed25519_verify_shreds_host: no fdgpu_ed25519_shreds_prepare"; return -3; }
-  if( key_cnt > ctx->sh_keys ) { fd_err = "more keys than prepared"; return -1; }
+  FRONT_CTX( ctx ); FRONT_PREPARED( ctx->sh.max, "fdgpu_ed25519_shreds_prepare" );
+  fd_front const & f = ctx->sh;
+  if( key_cnt > f.keys ) { fd_err = "more keys than prepared"; return -1; }
   if( !cnt ) return 0;
   if( !arena || !desc || !out || ( key_cnt && !keys ) ) { fd_err = "NULL argument"; return -1; }
   int rc;
-  unsigned char const * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
-  unsigned long most = ctx->sh_max;
-  if( !d_arena ) {
-    /* any other host memory: the shreds go through the staging slot, one every FD_SHRED_STRIDE bytes */
-    if( ( rc = sync_ctx( ctx, 1 ) ) ) return rc;
-    unsigned long fit = ctx->max_payload / FD_SHRED_STRIDE;
-    if( !fit ) { fd_err = "the staging slot holds no shred"; return -1; }
-    if( most > fit ) most = fit;
-  }
+  unsigned char * d_arena;
+  unsigned long most = f.max;
+  if( ( rc = front_arena( ctx, arena, arena_sz, &d_arena, &most ) ) ) return rc;
+  if( !most ) { fd_err = "the staging slot holds no shred"; return -1; }
   if( ( rc = sync_begin( ctx ) ) ) return rc;
   hipStream_t st = ctx->stream;
   fd_slot & sl = ctx->slot[0];
-  if( key_cnt ) HIPCHK( hipMemcpyAsync( ctx->d_sh_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
+  if( key_cnt ) HIPCHK( hipMemcpyAsync( f.d_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
   std::vector<fdgpu_shred_desc_t> tmp( most < cnt ? most : cnt );
   for( unsigned long done=0UL; done<cnt; ) {
     /* the chunk: records up to the prepared count, signatures -- numbered here, in order -- up to the slots */
@@ -5263,7 +5292,7 @@ fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const
     while( done + n < cnt && n < most ) {
       fdgpu_shred_desc_t d = desc[ done + n ];
       if( d.key_idx != FD_SHRED_NO_SIG ) {
-        if( nsig == ctx->sh_sig ) break;
+        if( nsig == f.sig ) break;
         d.sig_idx = (unsigned int)nsig++;
       }
       if( !d_arena ) {
@@ -5276,18 +5305,12 @@ fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const
       }
       tmp[ n++ ] = d;
     }
-    unsigned char const * da = d_arena; unsigned long dsz = arena_sz;
-    if( !d_arena ) {
-      dsz = FD_SHRED_STRIDE * n;
-      memset( sl.h_payload + dsz, 0, FD_ARENA_SLACK );
-      HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, dsz + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
-      da = sl.d_payload;
-    }
+    unsigned char * da = d_arena; unsigned long dsz = arena_sz;
+    if( !d_arena && ( rc = front_stage( sl, n, &da, &dsz, st ) ) ) return rc;
     HIPCHK( hipMemcpyAsync( ctx->d_sh_desc, tmp.data(), n * sizeof(fdgpu_shred_desc_t), hipMemcpyHostToDevice, st ), -2 );
-    if( ( rc = shreds_launch( ctx, da, dsz, ctx->d_sh_desc, n, nsig, ctx->d_sh_keys, key_cnt, ctx->d_sh_out,
-                              root ? ctx->d_sh_root : NULL, st ) ) ) return rc;
-    HIPCHK( hipMemcpyAsync( out + done, ctx->d_sh_out, n, hipMemcpyDeviceToHost, st ), -2 );
-    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, ctx->d_sh_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
+    if( ( rc = shreds_launch( ctx, da, dsz, ctx->d_sh_desc, n, nsig, f.d_keys, key_cnt, f.d_out, root ? f.d_root : NULL, st ) ) ) return rc;
+    HIPCHK( hipMemcpyAsync( out + done, f.d_out, n, hipMemcpyDeviceToHost, st ), -2 );
+    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, f.d_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
     if( stream_wait( ctx, st, 1 ) ) return -2;
     done += n;
   }
@@ -5299,45 +5322,27 @@ fdgpu_ed25519_verify_shreds_host( fdgpu_ed25519_ctx_t * ctx, unsigned char const
 extern "C" int
 fdgpu_ed25519_fec_prepare( fdgpu_ed25519_ctx_t * ctx, unsigned long max_sets, unsigned long max_members,
                            unsigned long max_keys ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_fec_prepare: the context has faulted"; return -3; }
+  FRONT_CTX( ctx );
   if( !max_sets || max_sets >= ( 1UL << 31 ) || !max_members || max_members >= ( 1UL << 31 ) ||
       !max_keys || max_keys > (unsigned long)FD_SHRED_NO_SIG ) {
     fd_err = "fdgpu_ed25519_fec_prepare: bad size"; return -1;
   }
-  if( max_sets <= ctx->fc_sets && max_members <= ctx->fc_members && max_keys <= ctx->fc_keys ) return 0;
+  if( max_sets <= ctx->fc.max && max_members <= ctx->fc_members && max_keys <= ctx->fc.keys ) return 0;
   HIPCHK( hipSetDevice( ctx->device ), -2 );
-  if( max_sets    < ctx->fc_sets    ) max_sets    = ctx->fc_sets;
+  if( max_sets    < ctx->fc.max     ) max_sets    = ctx->fc.max;
   if( max_members < ctx->fc_members ) max_members = ctx->fc_members;
-  if( max_keys    < ctx->fc_keys    ) max_keys    = ctx->fc_keys;
-  /* larger buffers: nothing of the context may still read the old ones */
-  HIPCHK( hipDeviceSynchronize(), -2 );
-  ctx->fc_sets = 0UL; ctx->fc_members = 0UL; ctx->fc_keys = 0UL; ctx->fc_sig = 0UL;
-  ctx_dev_free( ctx, &ctx->d_fc_pack ); ctx_dev_free( ctx, &ctx->d_fc_tdesc );  ctx_dev_free( ctx, &ctx->d_fc_code );
-  ctx_dev_free( ctx, &ctx->d_fc_flag ); ctx_dev_free( ctx, &ctx->d_fc_desc );   ctx_dev_free( ctx, &ctx->d_fc_member );
-  ctx_dev_free( ctx, &ctx->d_fc_out );  ctx_dev_free( ctx, &ctx->d_fc_root );   ctx_dev_free( ctx, &ctx->d_fc_expect );
-  ctx_dev_free( ctx, &ctx->d_fc_keys );
-  size_t ns = ctx->max_sig < ctx->max_txn ? ctx->max_sig : ctx->max_txn;
-  if( ns > max_sets ) ns = max_sets;
-  if( ns > ( 1UL << 24 ) ) ns = 1UL << 24;                   /* (128 ns + slack inside payload_off's 32 bits) */
-  size_t pack = FD_SHRED_SLOT * ns + 2UL * FD_ARENA_SLACK;
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_pack, pack ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_tdesc, ns * sizeof(fdgpu_txn_desc_t) ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_code, ns ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_flag, max_sets ), -2 );
+  if( max_keys    < ctx->fc.keys    ) max_keys    = ctx->fc.keys;
+  if( front_release( ctx, &ctx->fc ) ) return -2;
+  ctx->fc_members = 0UL;
+  ctx_dev_free( ctx, &ctx->d_fc_desc ); ctx_dev_free( ctx, &ctx->d_fc_member ); ctx_dev_free( ctx, &ctx->d_fc_expect );
   HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_desc, max_sets * sizeof(fdgpu_fec_desc_t) ), -2 );
   HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_member, max_members * sizeof(fdgpu_fec_member_t) ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_out, max_sets ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_root, 32UL * max_sets ), -2 );
   HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_expect, 32UL * max_sets ), -2 );
-  HIPCHK( ctx_dev_alloc( ctx, &ctx->d_fc_keys, 32UL * max_keys ), -2 );
-  HIPCHK( hipMemsetAsync( ctx->d_fc_pack, 0, pack, ctx->stream ), -2 );
-  HIPCHK( hipStreamSynchronize( ctx->stream ), -2 );
   int cus = 0;
   HIPCHK( hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, ctx->device ), -2 );
   ctx->fc_all = 4UL * (unsigned long)( cus > 0 ? cus : 1 );
-  ctx->fc_sets = max_sets; ctx->fc_members = max_members; ctx->fc_keys = max_keys; ctx->fc_sig = ns;
-  return 0;
+  ctx->fc_members = max_members;
+  return front_prepare( ctx, &ctx->fc, max_sets, max_keys );
 }
 
 /* the block that holds a set of most leaves: whole wavefronts */
@@ -5354,9 +5359,8 @@ fec_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char * d_arena, unsigned long ar
             unsigned long set_cnt, fdgpu_fec_member_t const * d_member, unsigned long member_cnt, unsigned long sig_cnt,
             unsigned char const * d_keys, unsigned long key_cnt, unsigned char const * d_expect, i8 * d_out,
             unsigned char * d_root, unsigned block, hipStream_t st ) {
-  if( sig_cnt )
-    hipLaunchKernelGGL( fd_shred_slot_kernel, dim3( (unsigned)( ( sig_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st,
-                        (uint4 *)ctx->d_fc_pack, ctx->d_fc_tdesc, (u32)sig_cnt );
+  fd_front const & f = ctx->fc;
+  front_slots( f, sig_cnt, st );
   /* block: the lanes that hold the largest set, known on the host; 0: not known (the descriptors are the device's).  A
      good set has cnt <= member_cnt, which bounds the block.  While every block of that size is resident at once, one
      launch: lanes without a leaf cost nothing then, and a block of four waves has one on each SIMD of its CU, where
@@ -5367,15 +5371,13 @@ fec_launch( fdgpu_ed25519_ctx_t * ctx, unsigned char * d_arena, unsigned long ar
   for( unsigned b=lo; b<=hi; b+=64U )
     hipLaunchKernelGGL( fd_fec_tree_kernel, dim3( (unsigned)set_cnt ), dim3(b), 4U * FD_FEC_LDS_WORDS( b ), st, d_arena, arena_sz,
                         d_desc, d_member, (u32)member_cnt, (u32)sig_cnt, (uint4 const *)d_keys, (u32)key_cnt,
-                        (uint4 const *)d_expect, (uint4 *)ctx->d_fc_pack, ctx->d_fc_tdesc, ctx->d_fc_flag, (uint4 *)d_root,
+                        (uint4 const *)d_expect, (uint4 *)f.d_pack, f.d_tdesc, f.d_flag, (uint4 *)d_root,
                         block ? 0U : b / 64U );
   HIPCHK( hipGetLastError(), -3 );
-  if( sig_cnt ) {
-    int rc = launch_batch( ctx, ctx->d_fc_pack, ctx->d_fc_tdesc, sig_cnt, sig_cnt, ctx->d_fc_code, NULL, st );
-    if( rc ) return rc;
-  } else ctx->last_path = FDGPU_PATH_NONE;                    /* a batch without signatures */
+  int rc = front_verify( ctx, f, sig_cnt, st );
+  if( rc ) return rc;
   hipLaunchKernelGGL( fd_fec_flag_kernel, dim3( (unsigned)( ( set_cnt + FD_WG - 1 ) / FD_WG ) ), dim3(FD_WG), 0, st, d_desc,
-                      (u32)set_cnt, (i8 const *)ctx->d_fc_flag, (i8 const *)ctx->d_fc_code, d_out );
+                      (u32)set_cnt, (i8 const *)f.d_flag, (i8 const *)f.d_code, d_out );
   HIPCHK( hipGetLastError(), -3 );
   return 0;
 }
@@ -5386,10 +5388,8 @@ fdgpu_ed25519_verify_fec_sets_device( fdgpu_ed25519_ctx_t * ctx, unsigned char *
                                       fdgpu_fec_member_t const * d_member, unsigned long member_cnt, unsigned long sig_cnt,
                                       unsigned char const * d_keys, unsigned long key_cnt, unsigned char const * d_expect,
                                       signed char * d_out, unsigned char * d_root, void * stream ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_fec_sets_device: the context has faulted"; return -3; }
-  if( !ctx->fc_sets ) { fd_err = "fdgpu_ed25519_verify_fec_sets_device: no fdgpu_ed25519_fec_prepare"; return -3; }
-  if( set_cnt > ctx->fc_sets || member_cnt > ctx->fc_members || sig_cnt > ctx->fc_sig || key_cnt > ctx->fc_keys ) {
+  FRONT_CTX( ctx ); FRONT_PREPARED( ctx->fc.max, "fdgpu_ed25519_fec_prepare" );
+  if( set_cnt > ctx->fc.max || member_cnt > ctx->fc_members || sig_cnt > ctx->fc.sig || key_cnt > ctx->fc.keys ) {
     fd_err = "batch larger than prepared"; return -1;
   }
   if( !set_cnt ) return 0;
@@ -5415,21 +5415,15 @@ fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t * ctx, unsigned char * a
                                     fdgpu_fec_member_t const * member, unsigned long member_cnt,
                                     unsigned char const * keys, unsigned long key_cnt, unsigned char const * expect,
                                     signed char * out, unsigned char * root ) {
-  if( !ctx ) { fd_err = "NULL ctx"; return -1; }
-  if( ctx->fault ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: the context has faulted"; return -3; }
-  if( !ctx->fc_sets ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: no fdgpu_ed25519_fec_prepare"; return -3; }
-  if( key_cnt > ctx->fc_keys ) { fd_err = "more keys than prepared"; return -1; }
+  FRONT_CTX( ctx ); FRONT_PREPARED( ctx->fc.max, "fdgpu_ed25519_fec_prepare" );
+  fd_front const & f = ctx->fc;
+  if( key_cnt > f.keys ) { fd_err = "more keys than prepared"; return -1; }
   if( !set_cnt ) return 0;
   if( !arena || !desc || !out || ( member_cnt && !member ) || ( key_cnt && !keys ) ) { fd_err = "NULL argument"; return -1; }
   int rc;
-  unsigned char * d_arena = region_dev( arena, arena_sz + FD_ARENA_SLACK );
-  unsigned long most = ctx->fc_members;
-  if( !d_arena ) {
-    /* any other host memory: the members' shreds go through the staging slot, one every FD_SHRED_STRIDE bytes */
-    if( ( rc = sync_ctx( ctx, 1 ) ) ) return rc;
-    unsigned long fit = ctx->max_payload / FD_SHRED_STRIDE;
-    if( most > fit ) most = fit;
-  }
+  unsigned char * d_arena;
+  unsigned long most = ctx->fc_members;                       /* members, each with its shred, of a chunk */
+  if( ( rc = front_arena( ctx, arena, arena_sz, &d_arena, &most ) ) ) return rc;
   for( unsigned long s=0UL; s<set_cnt; s++ ) {
     if( ( desc[s].flags & FD_FEC_CHECK_ROOT ) && !expect ) { fd_err = "FDGPU_FEC_CHECK_ROOT without expect"; return -1; }
     if( fec_need( desc[s], member_cnt ) > most ) { fd_err = "a set holds more members than a batch may"; return -1; }
@@ -5437,7 +5431,7 @@ fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t * ctx, unsigned char * a
   if( ( rc = sync_begin( ctx ) ) ) return rc;
   hipStream_t st = ctx->stream;
   fd_slot & sl = ctx->slot[0];
-  if( key_cnt ) HIPCHK( hipMemcpyAsync( ctx->d_fc_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
+  if( key_cnt ) HIPCHK( hipMemcpyAsync( f.d_keys, keys, 32UL * key_cnt, hipMemcpyHostToDevice, st ), -2 );
   std::vector<fdgpu_fec_desc_t>   td;
   std::vector<fdgpu_fec_member_t> tm;
   std::vector<unsigned int>       from;                       /* staged: where member k's shred came from */
@@ -5447,12 +5441,12 @@ fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t * ctx, unsigned char * a
     unsigned long n = 0UL, nm = 0UL, nsig = 0UL, big = 0UL;
     int any_fill = 0;
     td.clear(); tm.clear(); from.clear();
-    while( done + n < set_cnt && n < ctx->fc_sets ) {
+    while( done + n < set_cnt && n < f.max ) {
       fdgpu_fec_desc_t d = desc[ done + n ];
       unsigned long need = fec_need( d, member_cnt );
       if( nm + need > most ) break;
       if( d.key_idx != FD_SHRED_NO_SIG ) {
-        if( nsig == ctx->fc_sig ) break;
+        if( nsig == f.sig ) break;
         d.sig_idx = (unsigned int)nsig++;
       }
       if( !need ) d.member0 = 0xFFFFFFFFU;                     /* stays bad */
@@ -5483,23 +5477,18 @@ fdgpu_ed25519_verify_fec_sets_host( fdgpu_ed25519_ctx_t * ctx, unsigned char * a
     }
     if( !n ) { fd_err = "fdgpu_ed25519_verify_fec_sets_host: no signature slot"; return -1; }
     unsigned char * da = d_arena; unsigned long dsz = arena_sz;
-    if( !d_arena ) {
-      dsz = FD_SHRED_STRIDE * nm;
-      memset( sl.h_payload + dsz, 0, FD_ARENA_SLACK );
-      HIPCHK( hipMemcpyAsync( sl.d_payload, sl.h_payload, dsz + FD_ARENA_SLACK, hipMemcpyHostToDevice, st ), -2 );
-      da = sl.d_payload;
-    }
+    if( !d_arena && ( rc = front_stage( sl, nm, &da, &dsz, st ) ) ) return rc;
     HIPCHK( hipMemcpyAsync( ctx->d_fc_desc, td.data(), n * sizeof(fdgpu_fec_desc_t), hipMemcpyHostToDevice, st ), -2 );
     if( nm ) HIPCHK( hipMemcpyAsync( ctx->d_fc_member, tm.data(), nm * sizeof(fdgpu_fec_member_t), hipMemcpyHostToDevice, st ), -2 );
     if( expect ) HIPCHK( hipMemcpyAsync( ctx->d_fc_expect, expect + 32UL * done, 32UL * n, hipMemcpyHostToDevice, st ), -2 );
-    if( ( rc = fec_launch( ctx, da, dsz, ctx->d_fc_desc, n, ctx->d_fc_member, nm, nsig, ctx->d_fc_keys, key_cnt,
-                           expect ? ctx->d_fc_expect : NULL, ctx->d_fc_out, root ? ctx->d_fc_root : NULL, fec_block( big ), st ) ) ) return rc;
-    HIPCHK( hipMemcpyAsync( out + done, ctx->d_fc_out, n, hipMemcpyDeviceToHost, st ), -2 );
-    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, ctx->d_fc_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
+    if( ( rc = fec_launch( ctx, da, dsz, ctx->d_fc_desc, n, ctx->d_fc_member, nm, nsig, f.d_keys, key_cnt,
+                           expect ? ctx->d_fc_expect : NULL, f.d_out, root ? f.d_root : NULL, fec_block( big ), st ) ) ) return rc;
+    HIPCHK( hipMemcpyAsync( out + done, f.d_out, n, hipMemcpyDeviceToHost, st ), -2 );
+    if( root ) HIPCHK( hipMemcpyAsync( root + 32UL * done, f.d_root, 32UL * n, hipMemcpyDeviceToHost, st ), -2 );
     int back = !d_arena && any_fill && nm;
     if( back ) {
       fl.resize( n );
-      HIPCHK( hipMemcpyAsync( fl.data(), ctx->d_fc_flag, n, hipMemcpyDeviceToHost, st ), -2 );
+      HIPCHK( hipMemcpyAsync( fl.data(), f.d_flag, n, hipMemcpyDeviceToHost, st ), -2 );
       HIPCHK( hipMemcpyAsync( sl.h_payload, sl.d_payload, dsz, hipMemcpyDeviceToHost, st ), -2 );
     }
     if( stream_wait( ctx, st, 1 ) ) return -2;
@@ -5540,29 +5529,37 @@ fdgpu_sha256_batch_device( unsigned char const * d_data, unsigned long const * d
   return 0;
 }
 
-extern "C" int
-fdgpu_sha256_batch_host( int device, unsigned char const * data, unsigned long data_sz, unsigned long const * off,
-                         unsigned int const * sz, unsigned long cnt, unsigned char * hash ) {
+/* The host form of a hash batch: digests of HASH_SZ bytes by batch_device, which reads up to SLACK bytes past a
+   message; a message of SZ_LIM bytes or more is refused like one that leaves the buffer (1 << 32: none is). */
+template< unsigned long HASH_SZ, size_t SLACK, unsigned long SZ_LIM, class F > static int
+hash_batch_host( int device, unsigned char const * data, unsigned long data_sz, unsigned long const * off,
+                 unsigned int const * sz, unsigned long cnt, unsigned char * hash, F batch_device ) {
   if( !cnt ) return 0;
   for( unsigned long t=0; t<cnt; t++ )
-    if( off[t] > data_sz || sz[t] > data_sz - off[t] || sz[t] >= ( 1U << 29 ) ) { fd_err = "message out of buffer"; return -1; }
+    if( off[t] > data_sz || sz[t] > data_sz - off[t] || sz[t] >= SZ_LIM ) { fd_err = "message out of buffer"; return -1; }
   HIPCHK( hipSetDevice( device ), -2 );
   unsigned char * d_data = NULL, * d_hash = NULL; unsigned long * d_off = NULL; unsigned int * d_sz = NULL;
-  size_t slack = 128;                                   /* fd_sha256_bytes reads up to 67 bytes past a message */
   int rc = -2;
-  if( hipMalloc( (void **)&d_data, data_sz + slack ) != hipSuccess ||
+  if( hipMalloc( (void **)&d_data, data_sz + SLACK ) != hipSuccess ||
       hipMalloc( (void **)&d_off, cnt * sizeof(unsigned long) ) != hipSuccess ||
       hipMalloc( (void **)&d_sz, cnt * sizeof(unsigned int) ) != hipSuccess ||
-      hipMalloc( (void **)&d_hash, cnt * 32UL ) != hipSuccess ) { fd_err = "hipMalloc failed"; goto done; }
-  if( hipMemset( d_data + data_sz, 0, slack ) != hipSuccess ||
+      hipMalloc( (void **)&d_hash, cnt * HASH_SZ ) != hipSuccess ) { fd_err = "hipMalloc failed"; goto done; }
+  if( hipMemset( d_data + data_sz, 0, SLACK ) != hipSuccess ||
       ( data_sz && hipMemcpy( d_data, data, data_sz, hipMemcpyHostToDevice ) != hipSuccess ) ||
       hipMemcpy( d_off, off, cnt * sizeof(unsigned long), hipMemcpyHostToDevice ) != hipSuccess ||
       hipMemcpy( d_sz, sz, cnt * sizeof(unsigned int), hipMemcpyHostToDevice ) != hipSuccess ) { fd_err = "upload failed"; goto done; }
-  rc = fdgpu_sha256_batch_device( d_data, d_off, d_sz, cnt, d_hash, NULL );
-  if( !rc && hipMemcpy( hash, d_hash, cnt * 32UL, hipMemcpyDeviceToHost ) != hipSuccess ) { fd_err = "download failed"; rc = -2; }
+  rc = batch_device( d_data, d_off, d_sz, cnt, d_hash, NULL );
+  if( !rc && hipMemcpy( hash, d_hash, cnt * HASH_SZ, hipMemcpyDeviceToHost ) != hipSuccess ) { fd_err = "download failed"; rc = -2; }
 done:
   hipFree( d_data ); hipFree( d_off ); hipFree( d_sz ); hipFree( d_hash );
   return rc;
+}
+
+extern "C" int
+fdgpu_sha256_batch_host( int device, unsigned char const * data, unsigned long data_sz, unsigned long const * off,
+                         unsigned int const * sz, unsigned long cnt, unsigned char * hash ) {
+  /* (fd_sha256_bytes reads up to 67 bytes past a message) */
+  return hash_batch_host< 32UL, 128, 1UL << 29 >( device, data, data_sz, off, sz, cnt, hash, fdgpu_sha256_batch_device );
 }
 
 /* ---- batch SHA-512 ---------------------------------------------------- */
@@ -5582,26 +5579,8 @@ fdgpu_sha512_batch_device( unsigned char const * d_data, unsigned long const * d
 extern "C" int
 fdgpu_sha512_batch_host( int device, unsigned char const * data, unsigned long data_sz, unsigned long const * off,
                          unsigned int const * sz, unsigned long cnt, unsigned char * hash ) {
-  if( !cnt ) return 0;
-  for( unsigned long t=0; t<cnt; t++ )
-    if( off[t] > data_sz || sz[t] > data_sz - off[t] ) { fd_err = "message out of buffer"; return -1; }
-  HIPCHK( hipSetDevice( device ), -2 );
-  unsigned char * d_data = NULL, * d_hash = NULL; unsigned long * d_off = NULL; unsigned int * d_sz = NULL;
-  size_t slack = 256;                                   /* fd_sha512_bytes reads past the last block */
-  int rc = -2;
-  if( hipMalloc( (void **)&d_data, data_sz + slack ) != hipSuccess ||
-      hipMalloc( (void **)&d_off, cnt * sizeof(unsigned long) ) != hipSuccess ||
-      hipMalloc( (void **)&d_sz, cnt * sizeof(unsigned int) ) != hipSuccess ||
-      hipMalloc( (void **)&d_hash, cnt * 64UL ) != hipSuccess ) { fd_err = "hipMalloc failed"; goto done; }
-  if( hipMemset( d_data + data_sz, 0, slack ) != hipSuccess ||
-      hipMemcpy( d_data, data, data_sz, hipMemcpyHostToDevice ) != hipSuccess ||
-      hipMemcpy( d_off, off, cnt * sizeof(unsigned long), hipMemcpyHostToDevice ) != hipSuccess ||
-      hipMemcpy( d_sz, sz, cnt * sizeof(unsigned int), hipMemcpyHostToDevice ) != hipSuccess ) { fd_err = "upload failed"; goto done; }
-  rc = fdgpu_sha512_batch_device( d_data, d_off, d_sz, cnt, d_hash, NULL );
-  if( !rc && hipMemcpy( hash, d_hash, cnt * 64UL, hipMemcpyDeviceToHost ) != hipSuccess ) { fd_err = "download failed"; rc = -2; }
-done:
-  hipFree( d_data ); hipFree( d_off ); hipFree( d_sz ); hipFree( d_hash );
-  return rc;
+  /* (fd_sha512_bytes reads past the last block) */
+  return hash_batch_host< 64UL, 256, 1UL << 32 >( device, data, data_sz, off, sz, cnt, hash, fdgpu_sha512_batch_device );
 }
 
 /* ---- raw-payload batches (device fd_txn_parse + verify) ------------- */

@@ -262,6 +262,30 @@ def last_error() -> str:
     return load_library().fdgpu_last_error().decode()
 
 
+def _check(rc: int, name: str) -> None:
+    """A refusal of C call `name` as a RuntimeError, with the C return value as its second argument."""
+    if rc:
+        raise RuntimeError(f"{name}: {rc} {last_error()}", rc)
+
+
+def _keys_arg(keys):
+    """(uint8 array, key_cnt) of 32-byte keys given as bytes or as a uint8 array."""
+    if isinstance(keys, np.ndarray):
+        k = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        return k, len(k) // 32
+    k = np.frombuffer(bytes(keys) + b"\0", np.uint8)
+    return k, (len(k) - 1) // 32
+
+
+def _arena_arg(arena: np.ndarray, arena_sz: int | None, written: bool = False) -> int:
+    """arena_sz of a uint8 arena array: by default the array less ARENA_SLACK bytes, its slack."""
+    if arena_sz is None:
+        arena_sz = arena.nbytes - ARENA_SLACK
+    assert arena.dtype == np.uint8 and arena.flags.c_contiguous and 0 <= arena_sz <= arena.nbytes
+    assert arena.flags.writeable or not written
+    return arena_sz
+
+
 class DebugOpts(ctypes.Structure):
     """fdgpu_debug_opts_t: test / A/B choices for engine contexts created afterwards."""
     _fields_ = [("half", ctypes.c_int), ("half_force_slow", ctypes.c_uint), ("small_batch_max", ctypes.c_long),
@@ -366,19 +390,15 @@ def sha256_batch_host(msgs, device: int = 0) -> list[bytes]:
         pos += len(m)
     data = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", np.uint8)
     out = np.zeros((len(msgs), 32), np.uint8)
-    rc = L.fdgpu_sha256_batch_host(device, data.ctypes.data, pos, off.ctypes.data, sz.ctypes.data, len(msgs),
-                                   out.ctypes.data)
-    if rc:
-        raise RuntimeError(f"fdgpu_sha256_batch_host: {rc} {last_error()}", rc)
+    _check(L.fdgpu_sha256_batch_host(device, data.ctypes.data, pos, off.ctypes.data, sz.ctypes.data, len(msgs),
+                                     out.ctypes.data), "fdgpu_sha256_batch_host")
     return [out[i].tobytes() for i in range(len(msgs))]
 
 
 def sha256_batch_device(d_data: int, d_off: int, d_sz: int, cnt: int, d_hash: int, stream: int | None = None) -> None:
     """fdgpu_sha256_batch_device over raw device pointers: d_off u64 and d_sz u32 per message, 32 bytes a message to
     d_hash (16-byte aligned); d_data has 128 readable bytes behind its last message."""
-    rc = load_library().fdgpu_sha256_batch_device(d_data, d_off, d_sz, cnt, d_hash, stream)
-    if rc:
-        raise RuntimeError(f"fdgpu_sha256_batch_device: {rc} {last_error()}", rc)
+    _check(load_library().fdgpu_sha256_batch_device(d_data, d_off, d_sz, cnt, d_hash, stream), "fdgpu_sha256_batch_device")
 
 
 def raw_records(payload: np.ndarray, off: np.ndarray, sz: np.ndarray):
@@ -514,9 +534,7 @@ class Engine:
         """fdgpu_ed25519_sigs_prepare: the device buffers of verify_sigs_device and of verify_sigs_host over a
         registered region; a batch of cnt records with msg_bytes of messages needs 104 * cnt + msg_bytes at most.
         Raises on a refusal, with the C return value as the exception's second argument."""
-        rc = self.L.fdgpu_ed25519_sigs_prepare(self.ctx, max_packed_bytes)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_sigs_prepare: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_sigs_prepare(self.ctx, max_packed_bytes), "fdgpu_ed25519_sigs_prepare")
 
     def verify_sigs_host(self, arena: np.ndarray, desc: np.ndarray, arena_sz: int | None = None) -> np.ndarray:
         """fd_ed25519_verify codes (FDGPU_ERR_DESC for a bad descriptor) of the triples that desc (SIG_DESC_DTYPE)
@@ -524,32 +542,25 @@ class Engine:
         array less ARENA_SLACK bytes, its slack: if all of that lies in a registered region (host_register) the
         GPU reads the records in place.  Raises on a refusal, with the C return value as the exception's second
         argument."""
-        if arena_sz is None:
-            arena_sz = arena.nbytes - ARENA_SLACK
-        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and 0 <= arena_sz <= arena.nbytes
+        arena_sz = _arena_arg(arena, arena_sz)
         desc = np.ascontiguousarray(desc, dtype=SIG_DESC_DTYPE)
         out = np.zeros(max(len(desc), 1), np.int8)
-        rc = self.L.fdgpu_ed25519_verify_sigs_host(self.ctx, arena.ctypes.data, arena_sz,
-                                                   desc.ctypes.data, len(desc), out.ctypes.data)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_sigs_host: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_sigs_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
+                                                     out.ctypes.data), "fdgpu_ed25519_verify_sigs_host")
         return out[:len(desc)]
 
     def verify_sigs_device(self, d_arena: int, arena_sz: int, d_desc: int, cnt: int, msg_bytes: int, d_out: int,
                            stream: int | None = None) -> None:
         """Enqueue a batch of descriptors resident in device memory (raw device pointers; d_arena has ARENA_SLACK
         readable bytes behind arena_sz).  Raises on a refusal, with the C return value as the second argument."""
-        rc = self.L.fdgpu_ed25519_verify_sigs_device(self.ctx, d_arena, arena_sz, d_desc, cnt, msg_bytes, d_out, stream)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_sigs_device: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_sigs_device(self.ctx, d_arena, arena_sz, d_desc, cnt, msg_bytes, d_out, stream),
+               "fdgpu_ed25519_verify_sigs_device")
 
     # -- Merkle shreds: SHA-256 root, then the leader's signature ---------------
     def shreds_prepare(self, max_shreds: int, max_keys: int = 1) -> None:
         """fdgpu_ed25519_shreds_prepare: the device buffers of verify_shreds_device and verify_shreds_host.  Raises
         on a refusal, with the C return value as the exception's second argument."""
-        rc = self.L.fdgpu_ed25519_shreds_prepare(self.ctx, max_shreds, max_keys)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_shreds_prepare: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_shreds_prepare(self.ctx, max_shreds, max_keys), "fdgpu_ed25519_shreds_prepare")
 
     def verify_shreds_host(self, arena: np.ndarray, desc: np.ndarray, keys=b"", arena_sz: int | None = None,
                            want_root: bool = True):
@@ -560,20 +571,15 @@ class Engine:
         record, or None with want_root = False.  sig_idx is computed by the call.  Synchronous.  arena_sz defaults
         to the array less ARENA_SLACK bytes: if all of that lies in a registered region (host_register) the GPU
         reads the shreds in place.  Raises on a refusal, with the C return value as the exception's second argument."""
-        if arena_sz is None:
-            arena_sz = arena.nbytes - ARENA_SLACK
-        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and 0 <= arena_sz <= arena.nbytes
+        arena_sz = _arena_arg(arena, arena_sz)
         desc = np.ascontiguousarray(desc, dtype=SHRED_DESC_DTYPE)
-        k = np.frombuffer(bytes(keys) + b"\0", np.uint8) if not isinstance(keys, np.ndarray) else \
-            np.ascontiguousarray(keys, np.uint8).reshape(-1)
-        key_cnt = (len(k) - (0 if isinstance(keys, np.ndarray) else 1)) // 32
+        k, key_cnt = _keys_arg(keys)
         out = np.zeros(max(len(desc), 1), np.int8)
         root = np.zeros((max(len(desc), 1), 32), np.uint8) if want_root else None
-        rc = self.L.fdgpu_ed25519_verify_shreds_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
-                                                     k.ctypes.data, key_cnt, out.ctypes.data,
-                                                     root.ctypes.data if want_root else None)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_shreds_host: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_shreds_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
+                                                       k.ctypes.data, key_cnt, out.ctypes.data,
+                                                       root.ctypes.data if want_root else None),
+               "fdgpu_ed25519_verify_shreds_host")
         return out[:len(desc)], (root[:len(desc)] if want_root else None)
 
     def verify_shreds_device(self, d_arena: int, arena_sz: int, d_desc: int, cnt: int, sig_cnt: int, d_keys: int,
@@ -582,18 +588,14 @@ class Engine:
         ARENA_SLACK readable bytes behind arena_sz, d_keys and d_root are 16-byte aligned, d_root may be None).
         The caller numbers the signature-checked records, sig_idx in [0, sig_cnt).  Raises on a refusal, with the C
         return value as the second argument."""
-        rc = self.L.fdgpu_ed25519_verify_shreds_device(self.ctx, d_arena, arena_sz, d_desc, cnt, sig_cnt, d_keys, key_cnt,
-                                                       d_out, d_root, stream)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_shreds_device: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_shreds_device(self.ctx, d_arena, arena_sz, d_desc, cnt, sig_cnt, d_keys, key_cnt,
+                                                         d_out, d_root, stream), "fdgpu_ed25519_verify_shreds_device")
 
     # -- FEC sets: the whole tree, root, proofs and verdict -----------------------
     def fec_prepare(self, max_sets: int, max_members: int, max_keys: int = 1) -> None:
         """fdgpu_ed25519_fec_prepare: the device buffers of verify_fec_sets_device and verify_fec_sets_host.  Raises
         on a refusal, with the C return value as the exception's second argument."""
-        rc = self.L.fdgpu_ed25519_fec_prepare(self.ctx, max_sets, max_members, max_keys)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_fec_prepare: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_fec_prepare(self.ctx, max_sets, max_members, max_keys), "fdgpu_ed25519_fec_prepare")
 
     def verify_fec_sets_host(self, arena: np.ndarray, desc: np.ndarray, member: np.ndarray, keys=b"", expect=None,
                              arena_sz: int | None = None, want_root: bool = True):
@@ -604,26 +606,21 @@ class Engine:
         under key key_idx of keys (32 bytes each).  expect: (n, 32) uint8 or None.  roots is (n, 32) uint8, or None
         with want_root = False.  Synchronous; in place if the arena lies in a registered region (host_register).
         Raises on a refusal, with the C return value as the exception's second argument."""
-        if arena_sz is None:
-            arena_sz = arena.nbytes - ARENA_SLACK
-        assert arena.dtype == np.uint8 and arena.flags.c_contiguous and arena.flags.writeable and 0 <= arena_sz <= arena.nbytes
+        arena_sz = _arena_arg(arena, arena_sz, written=True)
         desc = np.ascontiguousarray(desc, dtype=FEC_DESC_DTYPE)
         member = np.ascontiguousarray(member, dtype=FEC_MEMBER_DTYPE)
-        k = np.frombuffer(bytes(keys) + b"\0", np.uint8) if not isinstance(keys, np.ndarray) else \
-            np.ascontiguousarray(keys, np.uint8).reshape(-1)
-        key_cnt = (len(k) - (0 if isinstance(keys, np.ndarray) else 1)) // 32
+        k, key_cnt = _keys_arg(keys)
         if expect is not None:
             expect = np.ascontiguousarray(expect, np.uint8).reshape(-1)
             assert len(expect) == 32 * len(desc)
         out = np.zeros(max(len(desc), 1), np.int8)
         root = np.zeros((max(len(desc), 1), 32), np.uint8) if want_root else None
-        rc = self.L.fdgpu_ed25519_verify_fec_sets_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
-                                                       member.ctypes.data if len(member) else None, len(member),
-                                                       k.ctypes.data, key_cnt,
-                                                       expect.ctypes.data if expect is not None and len(expect) else None,
-                                                       out.ctypes.data, root.ctypes.data if want_root else None)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_fec_sets_host: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_fec_sets_host(self.ctx, arena.ctypes.data, arena_sz, desc.ctypes.data, len(desc),
+                                                         member.ctypes.data if len(member) else None, len(member),
+                                                         k.ctypes.data, key_cnt,
+                                                         expect.ctypes.data if expect is not None and len(expect) else None,
+                                                         out.ctypes.data, root.ctypes.data if want_root else None),
+               "fdgpu_ed25519_verify_fec_sets_host")
         return out[:len(desc)], (root[:len(desc)] if want_root else None)
 
     def verify_fec_sets_device(self, d_arena: int, arena_sz: int, d_desc: int, set_cnt: int, d_member: int, member_cnt: int,
@@ -633,10 +630,9 @@ class Engine:
         ARENA_SLACK readable bytes behind arena_sz; d_keys, d_expect and d_root are 16-byte aligned, the last two may
         be None).  The caller numbers the keyed sets, sig_idx in [0, sig_cnt).  Raises on a refusal, with the C
         return value as the second argument."""
-        rc = self.L.fdgpu_ed25519_verify_fec_sets_device(self.ctx, d_arena, arena_sz, d_desc, set_cnt, d_member, member_cnt,
-                                                         sig_cnt, d_keys, key_cnt, d_expect, d_out, d_root, stream)
-        if rc:
-            raise RuntimeError(f"fdgpu_ed25519_verify_fec_sets_device: {rc} {last_error()}", rc)
+        _check(self.L.fdgpu_ed25519_verify_fec_sets_device(self.ctx, d_arena, arena_sz, d_desc, set_cnt, d_member, member_cnt,
+                                                           sig_cnt, d_keys, key_cnt, d_expect, d_out, d_root, stream),
+               "fdgpu_ed25519_verify_fec_sets_device")
 
     # -- raw payloads: device fd_txn_parse + verify ---------------------------
     def verify_raw_host(self, payload: np.ndarray, off: np.ndarray, sz: np.ndarray, want_img: bool = False):
